@@ -5,8 +5,10 @@ One "step" = one pass of Issuer::verify (afx_verify_presentations_dev) over one 
 presentations whose struct-of-arrays fields are already resident in HBM.  N > 1: one process per GPU, each
 verifying its own batch (host-sharded, no collective on the data path); value = all ranks' presentations /
 max-over-ranks time.  Inputs are produced by the engine itself (GPU issue -> GPU show), 1 % are corrupted, and
-every status byte is checked.  The `cpu_baseline` leg times the ORACLE's restated CPU path (kind "port") on a
-bounded sample of the same inputs on this machine's host cores and cross-checks the GPU's status bytes.
+every status byte is checked.  A plain run does only that: set up, warm up, time --steps steps, print one JSON line
+(--dump-outputs DIR: and write the last step's outputs as .npy files).  --full adds everything else: the `cpu_baseline` leg
+times the ORACLE's restated CPU path (kind "port") on a bounded sample of the same inputs on this machine's host cores and
+cross-checks the GPU's status bytes; the host-side legs; the rest of BASELINE.json's matrix as config.secondary.
 """
 import argparse
 import ctypes as C
@@ -231,6 +233,33 @@ def corrupt(pres, count, seed):
     return want
 
 
+DUMP_BUDGET = 64 << 20   # bytes of --dump-outputs in all
+
+
+def dump_outputs(dirname, arrays, count, prefix="", budget=DUMP_BUDGET):
+    """--dump-outputs: every output of the timed path's last step as <dirname>/<prefix><name>.npy in float32 (status and byte
+    arrays: small integers, exact).  `arrays` maps a name to (array, axis of its `count` items).  When they exceed `budget` bytes
+    in all, every array keeps the same fixed, seeded sample of items (its indices: <prefix>sample_index.npy), so that two builds
+    run with the same arguments compare output for output."""
+    os.makedirs(dirname, exist_ok=True)
+    per_item = sum(np.asarray(a).size // count * 4 for a, _ in arrays.values())
+    idx = None
+    if per_item * count > budget:
+        keep = max(1, budget // (per_item + 8))
+        idx = np.sort(np.random.default_rng(0xD0517).choice(count, size=keep, replace=False))
+        np.save(os.path.join(dirname, prefix + "sample_index.npy"), idx.astype(np.float64))
+    for name, (a, axis) in arrays.items():
+        a = np.asarray(a)
+        if idx is not None:
+            a = np.take(a, idx, axis=axis)
+        np.save(os.path.join(dirname, prefix + name + ".npy"), a.astype(np.float32))
+
+
+def rank_prefix(rank):
+    """--dump-outputs file names: rank 0's outputs are <name>.npy, another rank's rank<r>_<name>.npy"""
+    return "rank%d_" % rank if rank else ""
+
+
 def bench_issue(args, afx, batch, torch, dist, rank, world, local_rank, embedded=None):
     """secondary metric: credentials issued / s, C5 = 2^20 issuances, 16 attributes S x8 P x4 E x4.
     embedded = {"modes": [...], "steps": K, "warmup": W}: called from the C3 run (N = 1) for the line's config.secondary - the same
@@ -282,8 +311,8 @@ def bench_issue(args, afx, batch, torch, dist, rank, world, local_rank, embedded
             step()
         torch.cuda.synchronize()
         assert UNCHECKED or not status.cpu().numpy().any(), "issue failed"
-        # parity spot check of the first 64 credentials against the CPU oracle (checker only)
-        if rank == 0 and not args.no_cpu_baseline and not UNCHECKED:
+        # parity spot check of the first 64 credentials against the CPU oracle (checker only; --full)
+        if rank == 0 and args.full and not args.no_cpu_baseline and not UNCHECKED:
             import oracle
             octx = octx or oracle.Ctx(params, key, ip)
             h = {k: v[..., :64, :].cpu().numpy() for k, v in d_out.items()}
@@ -304,11 +333,14 @@ def bench_issue(args, afx, batch, torch, dist, rank, world, local_rank, embedded
         valu = valu_side(issuer, count, sum(kt[k]["ms_per_step"] for k in kt if k in MSM_KERNELS + FIELD_KERNELS))
         secret_terms = issuer.plan_stats()["secret_terms"]
         issuer.set_timing(False)
+        if args.dump_outputs and not embedded:   # what afx_issue_dev returned: the issuance SoA and the status bytes
+            dump_outputs(args.dump_outputs, dict({k: (v.cpu().numpy(), v.dim() - 2) for k, v in d_out.items()}, status=(status.cpu().numpy(), 0)),
+                         count, rank_prefix(rank), DUMP_BUDGET // world)
         assert UNCHECKED or not status.cpu().numpy().any(), "issue failed in the timed steps"
         if dist is not None:
             elapsed = dist.max_over_ranks(elapsed)
         cpu = None
-        if rank == 0 and world == 1 and not args.no_cpu_baseline and not embedded:   # the CPU baseline is an N=1 figure
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not embedded:   # the CPU baseline is an N=1 figure
             S = 256
             hin = {k: v[..., :S, :].cpu().numpy() for k, v in d_in.items()}
             t0 = time.perf_counter()
@@ -412,11 +444,12 @@ def bench_show(args, afx, batch, torch, dist, rank, world, local_rank, embedded=
             step()
         torch.cuda.synchronize()
         assert not status.cpu().numpy().any(), "show failed"
-        # every presentation made here must verify on the issuer's side (GPU), and the first 16 must equal the oracle's bytes
-        pres = {f: o[f].cpu().numpy() for f in batch.PRES_FIELDS}
-        pres["enc"] = [{f: eo[f].cpu().numpy() for f in batch.ENC_FIELDS}]
-        assert not batch.verify_presentations(issuer, shape, pres).any(), "a shown presentation does not verify"
-        if rank == 0 and not args.no_cpu_baseline:
+        # (--full) every presentation made here must verify on the issuer's side (GPU), and the first 16 must equal the oracle's bytes
+        if args.full:
+            pres = {f: o[f].cpu().numpy() for f in batch.PRES_FIELDS}
+            pres["enc"] = [{f: eo[f].cpu().numpy() for f in batch.ENC_FIELDS}]
+            assert not batch.verify_presentations(issuer, shape, pres).any(), "a shown presentation does not verify"
+        if rank == 0 and args.full and not args.no_cpu_baseline:
             import oracle
             octx = octx or oracle.Ctx(params, None, ip)
             for i in range(16):
@@ -437,6 +470,11 @@ def bench_show(args, afx, batch, torch, dist, rank, world, local_rank, embedded=
         valu = valu_side(user, count, sum(kt[k]["ms_per_step"] for k in kt if k in MSM_KERNELS + FIELD_KERNELS))
         secret_terms = user.plan_stats()["secret_terms"]
         user.set_timing(False)
+        if args.dump_outputs and not embedded:   # what afx_show_dev returned: the presentation SoA, its proof of encryption, the status bytes
+            outs = {k: (v.cpu().numpy(), v.dim() - 2) for k, v in o.items()}
+            outs.update({"enc0_" + k: (v.cpu().numpy(), v.dim() - 2) for k, v in eo.items()})
+            outs["status"] = (status.cpu().numpy(), 0)
+            dump_outputs(args.dump_outputs, outs, count, rank_prefix(rank), DUMP_BUDGET // world)
         if dist is not None:
             elapsed = dist.max_over_ranks(elapsed)
         ab = 32 * n + n + 96 + 32 + 128 + 96 + 64 + 32 + 32 + 907   # credential + keypair + randomness read, presentation written
@@ -898,6 +936,11 @@ def main():
     ap.add_argument("--dist-backend-fallback", default=None, help=argparse.SUPPRESS)   # set by launch_ranks on its second launch: why the first one failed
     ap.add_argument("--preflight", action="store_true", help="check that --gpus N can run here (devices and their PCI ids, RCCL, free HBM, host "
                     "memory, the library), print one JSON line and exit 0 / 1 without running anything")
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline: the host-side legs (host-pointer, wire blob, "
+                    "small call, group API), the CPU-oracle baseline and parity checks, config.secondary (C3), the GPU re-verification of "
+                    "shown presentations (show).  Default off: a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path returned in its last "
+                    "step as DIR/<name>.npy (float32; at most 64 MB in all: a fixed, seeded sample of the items when larger)")
     args = ap.parse_args()
 
     if args.preflight:
@@ -998,6 +1041,8 @@ def main():
     if dist is not None:
         elapsed = dist.max_over_ranks(elapsed)
     got = status.cpu().numpy()
+    if args.dump_outputs:   # what afx_verify_presentations_dev returned to its caller: one status byte per presentation
+        dump_outputs(args.dump_outputs, {"status": (got, 0)}, count, rank_prefix(rank), DUMP_BUDGET // world)
     assert UNCHECKED or np.array_equal(got, want), "status mismatch after the timed steps"
     ranks_seen, had_group = 1, dist is not None
     pg_backend = pg_fallback = None
@@ -1015,7 +1060,7 @@ def main():
     pcie = wire_rate = None
     group_rate = group_items = group_err = None
     reps = max(1, args.host_reps)
-    if rank == 0:
+    if rank == 0 and args.full:
         hsoa, keep_h = batch.presentation_soa(pres)
         hst = np.full(count, 255, np.uint8)
         pcie = spread(timed_reps(lambda: afx.check(afx.lib().afx_verify_presentations(issuer.h, C.byref(shape), C.byref(hsoa), count, hst.ctypes.data)), count, reps))
@@ -1056,7 +1101,7 @@ def main():
                 group_err = "%s: %s" % (type(e).__name__, e)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU baseline is an N=1 figure
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:   # the CPU baseline is an N=1 figure
         import oracle   # ORACLE: only here, as the timed CPU baseline and the checker
         olib = oracle.load(native=True)
         olib.afxo_ctx_new.restype = C.c_void_p
@@ -1094,7 +1139,7 @@ def main():
     # the rest of BASELINE.json's matrix in the same line (N = 1, the C3 run): C2, C5 in the library's default mode and with the
     # fast tables, show likewise - a few steps each, every result checked (statuses; bytes of the first items against the oracle)
     secondary = None
-    if rank == 0 and world == 1 and args.workload == "c3" and not args.no_secondary and not args.batch:
+    if rank == 0 and world == 1 and args.workload == "c3" and args.full and not args.no_secondary and not args.batch:
         issuer.close()
         issuer = None
         del pres
@@ -1127,6 +1172,7 @@ def main():
                        "step_pipelining": "2 streams" if args.pipelining else "off",
                        "secret_independent_addressing": {0: "nowhere (mode 0)", 1: "everywhere (mode 1)", 2: "prover-side calls (mode 2, the default)"}[secret_mode_of(args)],
                        "input_generation_s": round(gen_s, 2),
+                       "full": args.full,   # without --full the host-side legs, cpu_baseline and secondary are null: not run
                        # the host-side legs: median of `reps` repetitions each (the spread beside it), PCIe and staging inclusive
                        "host_pointer_api_presentations_per_s": pcie and pcie["median"], "host_pointer_api_spread": pcie,
                        "host_pointer_api_over_value": (pcie["median"] / (total / elapsed)) if pcie else None,

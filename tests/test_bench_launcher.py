@@ -81,6 +81,10 @@ def test_launcher_retries_once_on_gloo_when_the_process_group_did_not_form(tmp_p
         open(os.path.join(d, "launch_r%%s_%%d.json" %% (os.environ["RANK"], n)), "w").write(json.dumps(dict(argv=sys.argv[1:], port=os.environ["MASTER_PORT"], pid=os.getpid())))
         if "--dist-backend-fallback" not in sys.argv:
             if os.environ["RANK"] == "2":
+                import time
+                t0 = time.time()   # fail only once the other ranks of this launch have recorded themselves (the launcher stops them then)
+                while not all(os.path.exists(os.path.join(d, "launch_r%%d_0.json" %% r)) for r in (0, 1)) and time.time() - t0 < 30:
+                    time.sleep(0.01)
                 sys.stderr.write("rank 2: the nccl process group did not form\\n")
                 sys.exit(%d)
             import time

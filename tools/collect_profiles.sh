@@ -76,13 +76,13 @@ rm -rf $O/pmc_*_FETCH_SIZE $O/pmc_*_WRITE_SIZE $O/pmc_mix   # databases are larg
 # profiles/rNN_traffic.json whose kernel_sources_sha256 is this tree's)
 mkdir -p $R/profiles && cp $O/${TAG}_traffic.json $O/${TAG}_secret_traffic.json $R/profiles/
 cd $R
-python3 bench.py > $O/bench_c3.log 2>&1; line $O/bench_c3.log > $O/${TAG}_bench_c3.json
-python3 bench.py --workload c2 > $O/bench_c2.log 2>&1; line $O/bench_c2.log > $O/${TAG}_bench_c2.json
+python3 bench.py --full > $O/bench_c3.log 2>&1; line $O/bench_c3.log > $O/${TAG}_bench_c3.json
+python3 bench.py --workload c2 --full > $O/bench_c2.log 2>&1; line $O/bench_c2.log > $O/${TAG}_bench_c2.json
 for w in c5 show; do
-  python3 bench.py --workload $w > $O/bench_$w.log 2>&1; line $O/bench_$w.log > $O/${TAG}_bench_$w.json
-  python3 bench.py --workload $w --secret-mode 0 --no-cpu-baseline > $O/bench_${w}_mode0.log 2>&1; line $O/bench_${w}_mode0.log > $O/${TAG}_bench_${w}_fast_tables.json
+  python3 bench.py --workload $w --full > $O/bench_$w.log 2>&1; line $O/bench_$w.log > $O/${TAG}_bench_$w.json
+  python3 bench.py --workload $w --secret-mode 0 --full --no-cpu-baseline > $O/bench_${w}_mode0.log 2>&1; line $O/bench_${w}_mode0.log > $O/${TAG}_bench_${w}_fast_tables.json
 done
-python3 bench.py --secret-mode 1 --no-cpu-baseline > $O/bench_c3_mode1.log 2>&1; line $O/bench_c3_mode1.log > $O/${TAG}_bench_c3_secret_everywhere.json
+python3 bench.py --secret-mode 1 --full --no-cpu-baseline > $O/bench_c3_mode1.log 2>&1; line $O/bench_c3_mode1.log > $O/${TAG}_bench_c3_secret_everywhere.json
 # the small-call and mixed-request measurements of the round
 cd $R
 python3 tools/mixed_concurrency.py 64 16 > $O/${TAG}_mixed_concurrency.txt 2>&1
