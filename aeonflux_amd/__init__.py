@@ -217,6 +217,16 @@ def lib():
         _LIB.afx_group_show.argtypes = [C.c_void_p, C.POINTER(CredentialsSoA), C.POINTER(KeypairsSoA), C.POINTER(ShowRandomness), C.c_size_t,
                                         C.POINTER(PresentationOut), C.POINTER(Shape), C.c_void_p]
         _LIB.afx_group_issue.argtypes = [C.c_void_p, C.POINTER(AttributesSoA), C.POINTER(IssueRandomness), C.c_size_t, C.POINTER(IssuanceSoA), C.c_void_p]
+        # (serialized requests: wire_issue.cpp, which the host-simulation builds of the engine's first eight sources leave out)
+        if hasattr(_LIB, "afx_issue_wire"):
+            _LIB.afx_request_wire_header_bytes.restype = C.c_size_t
+            _LIB.afx_request_wire_header_bytes.argtypes = [C.c_uint32]
+            _LIB.afx_request_wire_parse.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            _LIB.afx_request_wire_section_bytes.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+            _LIB.afx_request_wire_pack.argtypes = [C.POINTER(AttributesSoA), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+            for name in ("afx_issue_wire", "afx_group_issue_wire"):
+                getattr(_LIB, name).argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(IssueRandomness), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                                C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         if hasattr(_LIB, "afx_issuer_keygen"):
             _LIB.afx_issuer_keygen.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p]
     return _LIB

@@ -1783,6 +1783,25 @@ __global__ void __launch_bounds__(AFX_BLOCK) k_aos_to_soa(const uint8_t* __restr
   dst[1] = b;
 }
 
+// the inverse: struct-of-arrays rows [row][count][32] -> wire records (`cells` 32-byte cells per item), cell c of a record taken from
+// row row_of_cell[c]; an item whose status byte is not 0 gets a record of zeros (status == null: every item is copied)
+__global__ void __launch_bounds__(AFX_BLOCK) k_soa_to_aos(const uint8_t* __restrict__ soa, uint8_t* __restrict__ rec,
+                                                          const uint32_t* __restrict__ row_of_cell, const uint8_t* __restrict__ status,
+                                                          uint32_t cells, uint32_t count) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;   // t = item * cells + cell: the record writes are coalesced
+  if (t >= (uint64_t)cells * count) return;
+  const uint32_t item = (uint32_t)(t / cells), cell = (uint32_t)(t % cells);
+  uint4* dst = reinterpret_cast<uint4*>(rec + t * 32);
+  uint4 a = make_uint4(0, 0, 0, 0), b = a;
+  if (!status || status[item] == 0) {
+    const uint4* src = reinterpret_cast<const uint4*>(soa + ((uint64_t)row_of_cell[cell] * count + item) * 32);
+    a = src[0];
+    b = src[1];
+  }
+  dst[0] = a;
+  dst[1] = b;
+}
+
 // ---------------------------------------------------------------------------------------------
 // host-callable launch wrappers (engine.cpp is plain C++ and never sees a kernel symbol)
 // ---------------------------------------------------------------------------------------------
@@ -1981,5 +2000,11 @@ hipError_t afxk_validate(hipStream_t s, const uint8_t* enc, uint8_t* ok, uint8_t
 hipError_t afxk_aos_to_soa(hipStream_t s, const uint8_t* rec, uint8_t* soa, const uint32_t* row_of_cell, uint32_t cells, uint32_t count) {
   const uint64_t n = (uint64_t)cells * count;
   hipLaunchKernelGGL(k_aos_to_soa, dim3((uint32_t)((n + AFX_BLOCK - 1) / AFX_BLOCK)), dim3(AFX_BLOCK), 0, s, rec, soa, row_of_cell, cells, count);
+  return hipGetLastError();
+}
+hipError_t afxk_soa_to_aos(hipStream_t s, const uint8_t* soa, uint8_t* rec, const uint32_t* row_of_cell, const uint8_t* status, uint32_t cells, uint32_t count) {
+  const uint64_t n = (uint64_t)cells * count;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_soa_to_aos, dim3((uint32_t)((n + AFX_BLOCK - 1) / AFX_BLOCK)), dim3(AFX_BLOCK), 0, s, soa, rec, row_of_cell, status, cells, count);
   return hipGetLastError();
 }

@@ -718,6 +718,9 @@ int afx::Session::launch() {
     for (auto& p : plans) ps.push_back(p.get());
     rc = run_plans_fitting(c, lane, ps.data(), ps.size());
   }
+  if (!rc)
+    for (auto& f : post)
+      if ((rc = f())) break;
   if (!rc && out_used && !outs.empty()) AFX_HIP(hipMemcpyAsync(L.pin, L.staging_out.p, out_used, hipMemcpyDeviceToHost, s));
   return rc;
 }

@@ -84,13 +84,14 @@ struct Session {
   struct Out { uint8_t* dst; size_t pin_off, len; };
   std::vector<Out> outs;
   std::vector<std::function<int()>> pre;            // launches that run after the upload and before the plans (k_aos_to_soa of a serialized batch)
+  std::vector<std::function<int()>> post;           // launches that run after the plans and before the download (k_soa_to_aos of a serialized response)
   // `shared`: a session of the context's coalescer (afx_ctx::co) - it is the context's `session` only while one call stages into it
   explicit Session(afx_ctx* ctx, bool shared_ = false) : c(ctx), shared(shared_) { if (!shared) c->session = this; }
   ~Session() { if (!shared && c->session == this) c->session = nullptr; }   // (a shared session's last owner may be a caller that no longer holds the context)
   Session(const Session&) = delete;
   Session& operator=(const Session&) = delete;
-  bool empty() const { return plans.empty() && outs.empty() && pre.empty() && in_used == 0 && out_used == 0; }
-  void drop() { plans.clear(); outs.clear(); pre.clear(); slots.clear(); in_used = out_used = 0; }
+  bool empty() const { return plans.empty() && outs.empty() && pre.empty() && post.empty() && in_used == 0 && out_used == 0; }
+  void drop() { plans.clear(); outs.clear(); pre.clear(); post.clear(); slots.clear(); in_used = out_used = 0; }
   int ensure_images(size_t in_bytes, size_t out_bytes);   // device staging + pinned images of at least these sizes (only while empty)
   // flush() = launch() + complete(): everything is enqueued on the lane's stream by launch() (the context's host state is used:
   // under afx_ctx::mu), complete() waits for the stream and scatters the results (no context state: the coalescer runs it unlocked)

@@ -129,3 +129,45 @@ def unpack_issuances(blob):
     c = lambda a: np.ascontiguousarray(a)
     iss = {"t": c(rec[0]), "U": c(rec[1]), "V": c(rec[2]), "challenge": c(rec[3]), "responses": c(rec[4:4 + nr])}
     return kinds, c(rec[4 + nr:]), iss
+
+
+# ---- CredentialRequest batches ("AFXR" v1) and Issuer::issue over them --------------------------------
+def pack_requests(kinds, values):
+    """kinds: AFX_ATTR_* per position; values [n,count,32] -> one AFXR section"""
+    n = len(kinds)
+    values = np.asarray(values, dtype=np.uint8)
+    assert values.ndim == 3 and values.shape[0] == n and values.shape[2] == 32
+    count = values.shape[1]
+    h = b"AFXR" + struct.pack("<4I", 1, count, n, n) + bytes(kinds)
+    h += bytes(-len(h) % 32)
+    return h + np.ascontiguousarray(values.transpose(1, 0, 2)).tobytes()
+
+
+def unpack_requests(blob):
+    """one AFXR section -> (kinds, values [n,count,32])"""
+    assert blob[:4] == b"AFXR"
+    ver, count, cells, n = struct.unpack("<4I", blob[4:20])
+    assert ver == 1 and cells == n
+    kinds = list(blob[20:20 + n])
+    o = (20 + n + 31) & ~31
+    assert len(blob) == o + count * n * 32
+    rec = np.frombuffer(blob, dtype=np.uint8, count=count * n * 32, offset=o).reshape(count, n, 32)
+    return kinds, np.ascontiguousarray(rec.transpose(1, 0, 2))
+
+
+def issue_wire(ctx, blob, rnd):
+    """afx_issue_wire (afx_group_issue_wire for a Group): a stream of AFXR sections -> (AFXI response bytes, status per request in
+    stream order).  rnd: dict t_wide [count,64], U_wide [count,64], rng_seed [count,32] in stream order."""
+    import ctypes as C
+    from . import IssueRandomness, check, lib
+    fn = lib().afx_group_issue_wire if hasattr(ctx, "member") else lib().afx_issue_wire
+    out_len, cnt = C.c_size_t(0), C.c_size_t(0)
+    check(fn(ctx.h, blob, len(blob), None, None, 0, C.byref(out_len), None, 0, C.byref(cnt)))
+    arrs = {k: np.ascontiguousarray(rnd[k], dtype=np.uint8) for k in ("t_wide", "U_wide", "rng_seed")}
+    for k, w in (("t_wide", 64), ("U_wide", 64), ("rng_seed", 32)):
+        assert arrs[k].size >= cnt.value * w, k
+    r = IssueRandomness(arrs["t_wide"].ctypes.data, arrs["U_wide"].ctypes.data, arrs["rng_seed"].ctypes.data)
+    out = np.zeros(max(1, out_len.value), np.uint8)
+    status = np.full(max(1, cnt.value), 255, np.uint8)
+    check(fn(ctx.h, blob, len(blob), C.byref(r), out.ctypes.data, out.size, C.byref(out_len), status.ctypes.data, status.size, C.byref(cnt)))
+    return out[:out_len.value].tobytes(), status[:cnt.value]

@@ -153,6 +153,7 @@ int afx_ctx_set_strict(afx_ctx* ctx, int enable);
  * scalars take the per-item window path instead (64 additions per term, whatever the key): running time independent of
  * the key, 3-5 % slower.  The reference computes these products with dalek's constant-time `*` / `multiscalar_mul`
  * (src/nizk/presentation.rs:342-351, src/amacs.rs:267-270); DESIGN.md section 1 "Secrets" (the threat model: docs/HISTORY.md section 1).
+ * It applies to every call that multiplies by the key: afx_issue* (afx_issue_wire too), afx_verify_presentations*.
  * Results are identical in both modes. */
 int afx_ctx_set_fixed_key_schedule(afx_ctx* ctx, int enable);
 
@@ -160,7 +161,7 @@ int afx_ctx_set_fixed_key_schedule(afx_ctx* ctx, int enable);
  * witnesses - with dalek's constant-time `*` / `multiscalar_mul` (src/amacs.rs:267-270, src/nizk/presentation.rs:162-184, zkp's
  * Prover), whose table lookups read every entry and select.  This engine's INSTRUCTION stream never depends on a per-item secret
  * in any mode; what the mode decides is whether the window digit of a secret may pick WHICH table entry a lane gathers from HBM:
- *   AFX_SECRETS_PROVER_SIDE (2, the default of a new context): not on the prover-side calls - afx_issue*, afx_show* and the
+ *   AFX_SECRETS_PROVER_SIDE (2, the default of a new context): not on the prover-side calls - afx_issue* (afx_issue_wire too), afx_show* and the
  *     symmetric-key helpers (afx_keypairs_derive, afx_encrypt, afx_decrypt): every scalar of every multiscalar job there but the
  *     constant 1 is treated as a secret.  What a user of the crate gets from its constant-time arithmetic.  Issuer::verify runs
  *     the fast tables (its only secret is the issuer key, see afx_ctx_set_fixed_key_schedule).
@@ -202,7 +203,7 @@ int afx_ctx_set_small_batch_items(afx_ctx* ctx, uint32_t items);
  * from as many threads as a server has (src/issuer.rs:141-147); Issuer::issue (:111-124), CredentialIssuance::verify (:48-57) and
  * AnonymousCredential::show (src/credential.rs:37-46) likewise.  One such call costs one chain of field operations on a device
  * that is otherwise idle (0.8 ms), so calls that queue behind each other would cap a server at ~1.2 k calls/s whatever its thread
- * count.  Instead, host-pointer calls (afx_verify_presentations[_range,_wire,_wire_range], afx_issue[_range],
+ * count.  Instead, host-pointer calls (afx_verify_presentations[_range,_wire,_wire_range], afx_issue[_range,_wire],
  * afx_verify_issuances[_range,_wire], afx_show[_range]) of at most 512 items that arrive while another call's kernels run are
  * COLLECTED: each stages its rows - calls of one statement, shape and mode into the free item slots of ONE pass, so 64 callers of
  * one shape are one pass of 64 items - and sleeps until the flush that carries its rows completes.  The caller that opened a
@@ -487,6 +488,42 @@ int afx_group_verify_issuances(afx_group* group, const afx_attributes_soa* attrs
  * reports the length needed. */
 int afx_issuance_wire_pack(const afx_attributes_soa* attrs, const afx_issuance_soa* issuances, uint32_t n_responses, size_t count, uint8_t* blob,
                            size_t blob_cap, size_t* len_out);
+
+/* A batch of CredentialRequests of one attribute layout (user.rs:137-139: the attributes; the crate serialises none), same style:
+ *   header : "AFXR" | u32le version (1) | u32le count | u32le cells_per_record | u32le n_attributes
+ *            | kinds[n_attributes] (u8, AFX_ATTR_*) | zero pad to 32 B
+ *   records: count x n_attributes x 32 bytes, each record = the value of every attribute in position order (Sc for scalar kinds,
+ *            Pt = M1 for point kinds: what afx_attributes_soa.values holds)
+ * cells_per_record = n_attributes.  One CredentialRequest is a section with count = 1; a request stream is sections back to back.
+ * n_attributes = 0 is well formed (every item of such a section is MAC_CREATION against any context).  A kind above
+ * AFX_ATTR_SECRET_POINT, n_attributes > AFX_MAX_ATTRIBUTES, a wrong cells_per_record or a wrong length: AFX_E_BAD_ARGS. */
+size_t afx_request_wire_header_bytes(uint32_t n_attributes);   /* 0 if n_attributes > AFX_MAX_ATTRIBUTES */
+int afx_request_wire_parse(const uint8_t* blob, size_t len, uint32_t* n_attributes_out, uint8_t kinds_out[AFX_MAX_ATTRIBUTES],
+                           size_t* count_out, size_t* records_offset_out);
+/* Length (header + records) of the AFXR v1 section that starts at `blob`; AFX_E_BAD_ARGS if its header is malformed or it runs past `len`. */
+int afx_request_wire_section_bytes(const uint8_t* blob, size_t len, size_t* section_len_out);
+/* Write such a batch from column arrays (HOST pointers; values [n][count][32]): what a user sends.  blob == NULL only reports the
+ * length needed.  Bytes only. */
+int afx_request_wire_pack(const afx_attributes_soa* requests, size_t count, uint8_t* blob, size_t blob_cap, size_t* len_out);
+/* Issuer::issue over a stream of AFXR sections: request bytes in, AFXI bytes out, both transpositions on the GPU.
+ *  - rnd: host arrays in stream order (item i of the stream uses t_wide[i], U_wide[i], rng_seed[i]), as for afx_issue.
+ *  - out: one AFXI v1 section per request section, in the same order, with the same count and kinds and n_responses = ctx n + 5:
+ *    response section k answers request section k.  status[i] answers the i-th request of the stream; *count_out = their number.
+ *  - An item whose status is not AFX_ST_OK has a record of zeros (attribute values included).  A section whose n_attributes is not
+ *    the context's is all MAC_CREATION (amacs.rs:285-287); undecodable points and non-canonical scalars give what afx_issue gives.
+ *    Every other record is byte for byte what afx_issue + afx_issuance_wire_pack make of the same inputs.
+ *  - out == NULL: only *out_len (and *count_out) from the headers and the context's n; no device work, rnd may be NULL.
+ *  - AFX_E_BAD_ARGS, with nothing written to out or status, for out_cap < *out_len, status_cap < the item count or a malformed
+ *    section anywhere in the stream; AFX_E_NO_KEY for a context without the issuer key.
+ *  - Sections of one layout are merged into one batch wherever they stand.  Small batches of several layouts run as one set of
+ *    launches (as afx_issue_mixed), calls of at most 512 items are collected with other threads' calls (afx_ctx_set_coalescing), large
+ *    batches go through the two lanes in slices (as afx_issue). */
+int afx_issue_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, const afx_issue_randomness* rnd, uint8_t* out, size_t out_cap,
+                   size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out);
+/* ... over a group's devices: every merged batch is split over the members (afx_shard_bounds), each writing its own record range of
+ * `out`; a stream of at most afx_ctx_set_small_batch_items requests goes whole to one member, in turn.  Bytes equal afx_issue_wire's. */
+int afx_group_issue_wire(afx_group* group, const uint8_t* blob, size_t len, const afx_issue_randomness* rnd, uint8_t* out,
+                         size_t out_cap, size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out);
 
 /* ---- AnonymousCredential::show (src/credential.rs:37-46 -> src/nizk/presentation.rs:139-321) - */
 
