@@ -227,6 +227,13 @@ def lib():
             for name in ("afx_issue_wire", "afx_group_issue_wire"):
                 getattr(_LIB, name).argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(IssueRandomness), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                                 C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        # (the user side on bytes: wire_user.cpp, likewise left out of those builds)
+        if hasattr(_LIB, "afx_show_wire"):
+            _LIB.afx_issuance_wire_section_bytes.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+            for name in ("afx_verify_issuances_mixed_wire", "afx_group_verify_issuances_mixed_wire"):
+                getattr(_LIB, name).argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+            for name in ("afx_show_wire", "afx_group_show_wire"):
+                getattr(_LIB, name).argtypes = [C.c_void_p, C.POINTER(ShowGroup), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t]
         if hasattr(_LIB, "afx_issuer_keygen"):
             _LIB.afx_issuer_keygen.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p]
     return _LIB

@@ -133,8 +133,9 @@ def verify_issuances_mixed(ctx, items):
     return status
 
 
-def _show_args(kinds, values, t, U, V, keypairs, z_wide, rng_seed, enc_seeds=None, M2=None, m3=None):
-    """(CredentialsSoA, KeypairsSoA or None, ShowRandomness, PresentationOut, output dict, count, keepalive) of one layout's credentials"""
+def _show_args(kinds, values, t, U, V, keypairs, z_wide, rng_seed, enc_seeds=None, M2=None, m3=None, outputs=True):
+    """(CredentialsSoA, KeypairsSoA or None, ShowRandomness, PresentationOut, output dict, count, keepalive) of one layout's credentials
+    (outputs=False: no output arrays - an empty PresentationOut and dict, for afx_show_wire, which does not read them)"""
     n = len(kinds)
     values, t, U, V, z_wide, rng_seed = map(_u8, (values, t, U, V, z_wide, rng_seed))
     cnt = t.shape[0]
@@ -156,6 +157,8 @@ def _show_args(kinds, values, t, U, V, keypairs, z_wide, rng_seed, enc_seeds=Non
         keep.append(ka)
         kp = KeypairsSoA(*(ka[f].ctypes.data for f in ("a", "a0", "a1", "pk")))
     rnd = ShowRandomness(z_wide.ctypes.data, rng_seed.ctypes.data, enc_seeds.ctypes.data if nsp else None)
+    if not outputs:
+        return cs, kp, rnd, PresentationOut(), {}, cnt, keep
     o = {k: np.zeros((cnt, 32), np.uint8) for k in ("challenge", "C_x_0", "C_x_1", "C_V")}
     o["responses"] = np.zeros((3 + hs, cnt, 32), np.uint8)
     o["C_y"] = np.zeros((n, cnt, 32), np.uint8)

@@ -359,6 +359,22 @@ struct Stager {
     ops.push_back({ 3, rows, elem, dn, 0, off });
     return off;
   }
+  // add_rows() of a one-row array whose items lie in several host pieces (the records of one layout in several sections of a stream):
+  // piece k holds items [first_k, first_k + n_k) of the `total`; the device array is the one add_rows(.., 1, elem, total, first, n, dn)
+  // makes, filled piece by piece with no host copy in between
+  struct Piece { size_t first, n; const uint8_t* src; };
+  size_t add_rows_pieces(const std::vector<Piece>& pieces, size_t elem, size_t total, size_t first, size_t n, size_t dn) {
+    const size_t k0 = copies.size();
+    const size_t off = add_rows(pieces.at(0).src, 1, elem, total, 0, n, dn);   // (its one copy is replaced below)
+    if (copies.size() == k0) return off;   // a joining call that does not fit: nothing was staged
+    const size_t at = copies[k0].off;      // where item `first` lands
+    copies.resize(k0);
+    for (const Piece& p : pieces) {
+      const size_t lo = std::max(first, p.first), hi = std::min(first + n, p.first + p.n);
+      if (lo < hi) copies.push_back({ at + (lo - first) * elem, p.src + (lo - p.first) * elem, (hi - lo) * elem, false });
+    }
+    return off;
+  }
   uint8_t* in_base() const { return (uint8_t*)c->lane[ln].staging.p + in_at; }
   uint8_t* out_base() const { return (uint8_t*)c->lane[ln].staging_out.p + out_at; }
   uint8_t* dev(size_t off) const { return (off & OUT) ? out_base() + (off & ~OUT) : in_base() + off; }

@@ -1,0 +1,588 @@
+// The user side of the protocol on bytes (include/aeonflux_gpu.h afx_verify_issuances_mixed_wire, afx_show_wire).
+//  - CredentialIssuance::verify (the crate's src/issuer.rs:48-57) over a stream of AFXI sections, as afx_issue_wire writes them:
+//    sections of one layout are merged wherever they stand (and staged from where they lie), the records are transposed to
+//    struct-of-arrays on the GPU (k_aos_to_soa) and verified as afx_verify_issuances_wire verifies one section.
+//  - AnonymousCredential::show (src/credential.rs:37-46) straight into AFXP sections: afx_show_dev writes its outputs into the rows of
+//    one scratch region per pass, the revealed attribute values are read from the credential's own value rows, and k_soa_to_aos turns
+//    the region into AFXP records - zeros for an item that failed - which come back in one fetch.
+// Only bytes move on the host.  The scheduling is afx_issue_wire's (wire_issue.cpp): small batches share one set of launches, small
+// calls are collected with other threads' calls, large ones go through the two lanes in slices, and a group splits every batch.
+#include <atomic>
+#include <map>
+#include <memory>
+#include <string>
+#include <system_error>
+#include <thread>
+#include <vector>
+#include "kernels.h"
+#include "statements.hpp"
+
+namespace {
+
+uint32_t rd32(const uint8_t* b) { return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24); }
+void wr32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
+
+// does a request of several batches on this context leave its small batches with the collector's sessions (plans.cpp; as mixed.cpp)?
+bool joins_the_collector(afx_ctx* ctx) {
+  CtxLock probe(ctx, true);
+  return ctx->lock_depth == 1 && ctx->co.enabled && ctx->co.max_items && ctx->small_batch_items && !ctx->trace && !ctx->pipelining && !ctx->session;
+}
+
+// Every batch of a request on one context, as wire_issue.cpp run_batches runs them: `run(b)` does batch b whole; counts[b] == 0: nothing
+// to launch.  With the collector on, the small batches join the collecting session; otherwise they are assembled into ONE set of
+// launches of the request's own; a large batch runs by itself, in between.
+template <class Run>
+int run_batches(afx_ctx* ctx, const std::vector<size_t>& counts, Run&& run) {
+  size_t live = 0, only = 0;
+  for (size_t b = 0; b < counts.size(); b++)
+    if (counts[b]) { live++; only = b; }
+  if (live == 0) return AFX_OK;
+  if (live == 1) return run(only);
+  int rc = AFX_OK;
+  afx::Deferred deferred;
+  std::unique_ptr<afx::DeferScope> defer;
+  std::unique_ptr<CtxLock> lock;
+  std::unique_ptr<afx::Session> ses;
+  const bool join = joins_the_collector(ctx);
+  if (join) defer.reset(new afx::DeferScope(&deferred));
+  else lock.reset(new CtxLock(ctx));   // the session owns the context until its last flush
+  if (lock && ctx->small_batch_items && !ctx->trace && !ctx->session) {
+    ses.reset(new afx::Session(ctx));
+    if ((rc = ses->ensure_images(0, 0))) return rc;
+    uint64_t width = 0;   // as in mixed.cpp run_groups
+    for (size_t cnt : counts)
+      if (cnt && cnt <= ctx->small_batch_items) width += (cnt + 63) / 64;
+    ctx->merge_class = afx_ctx::merge_class_of(width);
+  }
+  struct WidthReset { afx_ctx* c; ~WidthReset() { if (c) c->merge_class = 0; } } width_reset = { ses ? ctx : nullptr };
+  try {   // (an exception must not pass the drain below: other threads' calls may sit in a session only this thread launches)
+    for (size_t b = 0; b < counts.size() && !rc; b++) {
+      if (!counts[b]) continue;
+      const bool collect = ses && counts[b] <= ctx->small_batch_items;
+      if (ses && !collect) {
+        if ((rc = ses->flush())) break;
+        ses->paused = true;
+      }
+      rc = run(b);
+      if (ses) ses->paused = false;
+      if (rc) set_error("batch " + std::to_string(b) + ": " + afx_last_error());
+    }
+  } catch (...) {
+    if (!join) throw;
+    rc = afx::exception_rc();
+  }
+  if (ses) {
+    if (rc) ses->drop();
+    else rc = ses->flush();
+    ses.reset();
+  }
+  if (join) {
+    CtxLock lk(ctx, true);
+    const int rc2 = afx::drain_deferred(ctx, deferred);   // (also after a failure: the staged rows point into this request's buffers)
+    if (!rc) rc = rc2;
+    defer.reset();
+  }
+  return rc;
+}
+
+// may small calls of a group go to any member (the members' settings alike, as group.cpp run_members requires)?
+bool members_alike(afx_group* g, uint32_t m) {
+  struct Set { uint32_t sb, chunk; bool strict, fixed, timing, trace; int secret; };
+  auto of = [](afx_ctx* c) { std::lock_guard<std::mutex> l(c->settings_mu); return Set{ c->small_batch_items, c->chunk_items, c->strict, c->fixed_key_schedule, c->timing, c->trace != nullptr, c->secret_mode }; };
+  const Set s0 = of(afx_group_member(g, 0));
+  if (s0.trace) return false;
+  for (uint32_t k = 1; k < m; k++) {
+    const Set s = of(afx_group_member(g, k));
+    if (s.sb != s0.sb || s.chunk != s0.chunk || s.strict != s0.strict || s.fixed != s0.fixed || s.timing != s0.timing || s.secret != s0.secret || s.trace) return false;
+  }
+  return true;
+}
+std::atomic<uint32_t> g_next_small{ 0 };
+
+// Runs body(k) for every member k of `group` on a thread of its own (member 0: the caller's thread); the first failure is returned.
+template <class Body>
+int on_members(afx_group* group, uint32_t m, Body&& body) {
+  std::vector<int> rcs(m, AFX_OK);
+  std::vector<std::string> errs(m);
+  auto one = [&](uint32_t k) {
+    GroupPin pin(group, k, k == 0);   // the member's thread on its device's NUMA node (member 0: the caller's thread, restored)
+    if ((rcs[k] = body(afx_group_member(group, k), k))) errs[k] = afx_last_error();   // (the error string is per thread)
+  };
+  std::vector<std::thread> threads;
+  for (uint32_t k = 1; k < m; k++) {
+    try { threads.emplace_back(one, k); } catch (const std::system_error&) { one(k); }
+  }
+  one(0);
+  for (std::thread& t : threads) t.join();
+  for (uint32_t k = 0; k < m; k++)
+    if (rcs[k]) { set_error("member " + std::to_string(k) + ": " + errs[k]); return rcs[k]; }
+  return AFX_OK;
+}
+
+// ---- CredentialIssuance::verify over AFXI streams -------------------------------------------------------------------------------
+
+struct ISection {
+  size_t off, hdr, count, first;   // bytes, header bytes, items, index of its first item in the stream
+  uint32_t n, nr;
+  uint8_t kinds[AFX_MAX_ATTRIBUTES];
+};
+// The issuances of one (n_attributes, n_responses, kinds), merged over the sections that carry it: their records stay where they lie
+// in the caller's blob (staged piece by piece); the statuses go to the caller's array when ONE section carries the layout, else to a
+// buffer of the batch's own, scattered afterwards.
+struct IBatch {
+  std::vector<size_t> secs;
+  size_t count = 0;
+  uint32_t n = 0, nr = 0;
+  uint8_t kinds[AFX_MAX_ATTRIBUTES];
+  bool fails = false;                  // a layout every item fails on (afx_verify_issuances_dev's fail_all): answered here
+  std::vector<Stager::Piece> pieces;   // the records [count][4 + nr + n][32], section by section
+  uint8_t* status = nullptr;           // [count]
+  std::vector<uint8_t> st_buf;
+};
+struct IStream {
+  std::vector<ISection> secs;
+  std::vector<IBatch> batches;   // in order of first appearance
+  size_t total = 0;
+};
+
+// Splits the stream into sections (every one parsed in full: a malformed one anywhere fails the call before anything runs) and merges
+// the sections of one layout.
+int parse_issuances(const uint8_t* blob, size_t len, uint32_t ctx_n, IStream& S) {
+  if (!blob && len) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  std::map<std::string, size_t> by_layout;
+  for (size_t off = 0; off < len;) {
+    size_t sl = 0, cnt = 0, rec = 0;
+    ISection s;
+    int rc = afx_issuance_wire_section_bytes(blob + off, len - off, &sl);
+    if (!rc) rc = afx_issuance_wire_parse(blob + off, sl, &s.n, s.kinds, &s.nr, &cnt, &rec);
+    if (rc) { set_error("section at byte " + std::to_string(off) + ": " + afx_last_error()); return rc; }
+    s.off = off; s.hdr = rec; s.count = cnt; s.first = S.total;
+    S.total += cnt;   // (< len / 32)
+    if (cnt) {
+      std::string key((const char*)&s.nr, sizeof s.nr);
+      key.append((const char*)s.kinds, s.n);   // (n is the key's length - 4)
+      auto it = by_layout.find(key);
+      if (it == by_layout.end()) {
+        it = by_layout.emplace(key, S.batches.size()).first;
+        S.batches.emplace_back();
+        IBatch& B = S.batches.back();
+        B.n = s.n; B.nr = s.nr;
+        memcpy(B.kinds, s.kinds, AFX_MAX_ATTRIBUTES);
+        // more attributes than generators, or a response count the statement does not have: every item fails (statements_prove.cpp
+        // afx_verify_issuances_dev), without a launch
+        B.fails = s.n > ctx_n || s.nr != ctx_n + 5;
+      }
+      S.batches[it->second].secs.push_back(S.secs.size());
+      S.batches[it->second].count += cnt;
+    }
+    S.secs.push_back(s);
+    off += sl;
+  }
+  return AFX_OK;
+}
+
+int check_issuances(const IStream& S, const uint8_t* status, size_t status_cap) {
+  if (status_cap < S.total || (!status && S.total)) { set_error("status buffer too small"); return AFX_E_BAD_ARGS; }
+  for (const IBatch& B : S.batches)
+    if (!B.fails && B.count > 0xffffffffu / 64) { set_error("too many issuances of one layout"); return AFX_E_BAD_ARGS; }
+  return AFX_OK;
+}
+
+// every batch's records (where they lie in the blob) and statuses; the batches nothing is launched for are answered here
+void prepare_issuances(IStream& S, const uint8_t* blob, uint8_t* status) {
+  for (IBatch& B : S.batches) {
+    if (B.fails) {
+      for (size_t k : B.secs) memset(status + S.secs[k].first, AFX_ST_VERIFICATION_FAILURE, S.secs[k].count);
+      continue;
+    }
+    size_t at = 0;
+    for (size_t k : B.secs) {
+      const ISection& s = S.secs[k];
+      B.pieces.push_back({ at, s.count, blob + s.off + s.hdr });
+      at += s.count;
+    }
+    if (B.secs.size() == 1) B.status = status + S.secs[B.secs[0]].first;
+    else { B.st_buf.assign(B.count, AFX_ST_VERIFICATION_FAILURE); B.status = B.st_buf.data(); }
+  }
+}
+void scatter_issuances(const IStream& S, uint8_t* status) {
+  for (const IBatch& B : S.batches) {
+    if (B.fails || B.secs.size() == 1) continue;
+    size_t at = 0;
+    for (size_t k : B.secs) {
+      const ISection& s = S.secs[k];
+      memcpy(status + s.first, B.status + at, s.count);
+      at += s.count;
+    }
+  }
+}
+
+// Items [first, first + n) of a batch, staged exactly as afx_verify_issuances_wire stages one section (statements.cpp), under the same
+// join key: a collected call of either front end may take item slots of the other's pass.
+int verify_records(afx_ctx* ctx, const IBatch& B, size_t first, size_t n) {
+  CtxLock lock__(ctx, true);
+  if (n == 0) return AFX_OK;
+  AFX_HIP(hipSetDevice(ctx->device));
+  const uint32_t na = B.n, nr = B.nr, cells = 4 + nr + na;
+  std::vector<uint32_t> row_of_cell(cells);
+  for (uint32_t r = 0; r < cells; r++) row_of_cell[r] = r;   // SoA rows in record order: t U V challenge responses[] values[]
+  struct { uint32_t n, nr; uint8_t kinds[AFX_MAX_ATTRIBUTES]; } jd;
+  memset(&jd, 0, sizeof jd);
+  jd.n = na; jd.nr = nr; memcpy(jd.kinds, B.kinds, AFX_MAX_ATTRIBUTES);
+  const PlanKey jkey = plan_key("VIW", &jd, sizeof jd, mode_flags(ctx));
+  const size_t total = B.count;
+  return host_pipe(ctx, n, [&](Stager& st, size_t off, size_t sn) -> int {
+    const size_t f0 = first + off;
+    st.layout_tag = 1;
+    const size_t dn = st.dev_items(sn);
+    // (one section: its records as afx_verify_issuances_wire stages them; several: the same region, filled section by section)
+    const size_t o_rec = B.pieces.size() == 1 ? st.add_rows(B.pieces[0].src, 1, (size_t)cells * 32, total, f0, sn, dn)
+                                              : st.add_rows_pieces(B.pieces, (size_t)cells * 32, total, f0, sn, dn),
+                 o_map = st.add((const uint8_t*)row_of_cell.data(), 4 * (size_t)cells),
+                 o_soa = st.reserve(dn * cells * 32), o_st = st.add(nullptr, dn);
+    st.plan_fetch(B.status, o_st, 1, 1, total, f0, sn, dn);
+    int rc = st.upload();
+    if (rc) return rc;
+    if (!st.app) {   // (a call that took item slots of an earlier call's pass: that call's transposition covers them)
+      hipStream_t strm = st.stream();
+      const uint8_t* rec_d = st.dev(o_rec);
+      uint8_t* soa_d = st.dev(o_soa);
+      const uint32_t* map_d = (const uint32_t*)st.dev(o_map);
+      const uint32_t dn_ = (uint32_t)dn;
+      auto transpose = [=]() -> int { AFX_HIP(afxk_aos_to_soa(strm, rec_d, soa_d, map_d, cells, dn_)); return AFX_OK; };
+      if (st.ses) st.ses->pre.push_back(transpose);
+      else if ((rc = transpose())) return rc;
+    }
+    auto rowp = [&](uint32_t r) { return st.dev(o_soa) + (size_t)r * dn * 32; };
+    afx_attributes_soa as;
+    memset(&as, 0, sizeof as);
+    as.n_attributes = na; memcpy(as.kinds, B.kinds, AFX_MAX_ATTRIBUTES);
+    as.values = rowp(4 + nr);
+    const afx_issuance_soa iss = { rowp(0), rowp(1), rowp(2), rowp(3), rowp(4) };
+    if ((rc = afx_verify_issuances_dev(ctx, &as, &iss, nr, dn, st.dev(o_st)))) return rc;
+    return st.fetch_all();
+  }, jkey);
+}
+
+std::vector<size_t> launch_counts(const IStream& S) {
+  std::vector<size_t> c(S.batches.size(), 0);
+  for (size_t b = 0; b < S.batches.size(); b++) c[b] = S.batches[b].fails ? 0 : S.batches[b].count;
+  return c;
+}
+
+// ---- AnonymousCredential::show into AFXP ----------------------------------------------------------------------------------------
+
+// the presentation shape afx_show gives a credential layout (statements_prove.cpp afx_show_dev; presentation.rs:293-320)
+afx_shape shape_of(const afx_credentials_soa& cr) {
+  afx_shape sh;
+  memset(&sh, 0, sizeof sh);
+  sh.n_attributes = cr.n_attributes;
+  uint32_t hs = 0, nsp = 0;
+  for (uint32_t i = 0; i < cr.n_attributes; i++) {
+    switch (cr.kinds[i]) {
+      case AFX_ATTR_PUBLIC_SCALAR: sh.kinds[i] = AFX_ENC_PUBLIC_SCALAR; break;
+      case AFX_ATTR_SECRET_SCALAR: sh.kinds[i] = AFX_ENC_SECRET_SCALAR; sh.hidden_scalar_indices[hs++] = (uint16_t)i; break;
+      case AFX_ATTR_SECRET_POINT: sh.kinds[i] = AFX_ENC_SECRET_POINT; sh.enc_indices[nsp++] = (uint16_t)i; break;
+      default: sh.kinds[i] = AFX_ENC_PUBLIC_POINT; break;
+    }
+  }
+  sh.n_hidden_scalars = hs;
+  sh.n_responses = 3 + hs;
+  sh.n_enc_proofs = nsp;
+  return sh;
+}
+
+// One afx_show_group as one AFXP section of the output.
+struct SJob {
+  const afx_show_group* g = nullptr;
+  afx_shape sh;
+  uint32_t cells = 0;
+  size_t out_off = 0, hdr = 0;
+  bool no_key = false;                 // SECRET_POINT attributes and no keypairs: NoSymmetricKey for every item, nothing launched
+  uint8_t* rec = nullptr;              // out + out_off + hdr: [count][cells][32]
+  uint8_t* status = nullptr;           // the caller's contiguous range, or st_buf (positions given)
+  std::vector<uint8_t> st_buf;
+};
+struct SPlan {
+  std::vector<SJob> jobs;
+  size_t out_len = 0, items = 0;
+};
+
+// The groups' sections and their length; every group whose layout afx_show refuses fails the call.  `arrays`: the full call also
+// checks the arrays afx_show would read (the size query reads none).
+int plan_show(afx_ctx* ctx, const afx_show_group* groups, size_t n_groups, bool arrays, SPlan& P) {
+  if (!groups && n_groups) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  P.jobs.resize(n_groups);
+  for (size_t gi = 0; gi < n_groups; gi++) {
+    const afx_show_group& G = groups[gi];
+    SJob& J = P.jobs[gi];
+    J.g = &G;
+    const afx_credentials_soa& cr = G.creds;
+    auto bad = [&](const char* why) { set_error("group " + std::to_string(gi) + ": " + why); return AFX_E_BAD_ARGS; };
+    if (cr.n_attributes == 0 || cr.n_attributes > ctx->n) return bad("credential attribute count does not fit the system parameters");
+    for (uint32_t i = 0; i < cr.n_attributes; i++)
+      if (cr.kinds[i] > AFX_ATTR_SECRET_POINT) return bad("unknown attribute kind");
+    if (G.count > 0xffffffffu / 64) return bad("too many credentials in one group");
+    J.sh = shape_of(cr);
+    J.cells = afx_wire_cells_per_record(&J.sh);
+    J.hdr = afx_wire_header_bytes(&J.sh);
+    const uint32_t nsp = J.sh.n_enc_proofs;
+    J.no_key = nsp && !G.keypairs;
+    if (arrays && G.count) {   // (afx_show_range's checks)
+      if (!cr.values || !cr.t || !cr.U || !cr.V || !G.rnd.z_wide || !G.rnd.rng_seed || (nsp && (!G.rnd.enc_seeds || !cr.M2 || !cr.m3)))
+        return bad("null batch array");
+      if (G.keypairs && nsp && (!G.keypairs->a || !G.keypairs->a0 || !G.keypairs->a1 || !G.keypairs->pk)) return bad("null keypair array");
+    }
+    J.out_off = P.out_len;
+    P.out_len += J.hdr + G.count * J.cells * 32;   // (< 2^26 * 2^10 * 2^5 per group)
+    P.items += G.count;
+  }
+  return AFX_OK;
+}
+
+// positions given: each < status_len and used once over all groups; not given: contiguous after the groups before (mixed.cpp)
+int check_positions(const afx_show_group* groups, size_t n_groups, size_t status_len) {
+  std::vector<uint8_t> used(status_len, 0);
+  size_t next = 0;
+  for (size_t g = 0; g < n_groups; g++) {
+    const afx_show_group& grp = groups[g];
+    for (size_t i = 0; i < grp.count; i++) {
+      const uint64_t p = grp.positions ? grp.positions[i] : (uint64_t)(next + i);
+      if (p >= status_len) { set_error("group " + std::to_string(g) + ": position outside the status array"); return AFX_E_BAD_ARGS; }
+      if (used[p]) { set_error("group " + std::to_string(g) + ": a status position is used twice"); return AFX_E_BAD_ARGS; }
+      used[p] = 1;
+    }
+    next += grp.count;
+  }
+  return AFX_OK;
+}
+
+// headers, the sections nothing is launched for, and where every group's statuses go
+void prepare_show(SPlan& P, uint8_t* out, uint8_t* status) {
+  size_t next = 0;
+  for (SJob& J : P.jobs) {
+    const afx_shape& sh = J.sh;
+    const size_t count = J.g->count;
+    uint8_t* h = out + J.out_off;
+    memset(h, 0, J.hdr);
+    memcpy(h, "AFXP", 4);
+    wr32(h + 4, 1); wr32(h + 8, (uint32_t)count); wr32(h + 12, J.cells);
+    wr32(h + 16, sh.n_attributes); wr32(h + 20, sh.n_responses); wr32(h + 24, sh.n_hidden_scalars); wr32(h + 28, sh.n_enc_proofs);
+    uint8_t* p = h + 32;
+    for (uint32_t i = 0; i < sh.n_attributes; i++) *p++ = sh.kinds[i];
+    for (uint32_t i = 0; i < sh.n_hidden_scalars; i++) { *p++ = (uint8_t)sh.hidden_scalar_indices[i]; *p++ = (uint8_t)(sh.hidden_scalar_indices[i] >> 8); }
+    for (uint32_t i = 0; i < sh.n_enc_proofs; i++) { *p++ = (uint8_t)sh.enc_indices[i]; *p++ = (uint8_t)(sh.enc_indices[i] >> 8); }
+    J.rec = h + J.hdr;
+    if (J.g->positions) { J.st_buf.assign(count, AFX_ST_VERIFICATION_FAILURE); J.status = J.st_buf.data(); }
+    else J.status = status + next;
+    next += count;
+    if (J.no_key) {   // CredentialError::NoSymmetricKey (presentation.rs:150-157), as afx_show answers it
+      memset(J.rec, 0, count * J.cells * 32);
+      memset(J.status, AFX_ST_NO_SYMMETRIC_KEY, count);
+    }
+  }
+}
+void scatter_show(const SPlan& P, uint8_t* status) {
+  for (const SJob& J : P.jobs)
+    if (J.g->positions)
+      for (size_t i = 0; i < J.g->count; i++) status[J.g->positions[i]] = J.st_buf[i];
+}
+std::vector<size_t> launch_counts(const SPlan& P) {
+  std::vector<size_t> c(P.jobs.size(), 0);
+  for (size_t b = 0; b < P.jobs.size(); b++) c[b] = P.jobs[b].no_key ? 0 : P.jobs[b].g->count;
+  return c;
+}
+
+// Items [first, first + n) of a group.  Per pass, one region of scratch holds the rows
+//   challenge | responses[3 + hs] | C_x_0 C_x_1 C_V | C_y[n] | 14 per proof of encryption | (pad to a multiple of 8 rows)
+// and the credential's value rows are staged right behind it, so that a revealed value's cell maps to its value row directly.
+// afx_show_dev fills the rows; k_soa_to_aos copies the region out as AFXP records (right after the plan, or the session's `post`),
+// fetched in one piece.
+int show_records(afx_ctx* ctx, const SJob& J, size_t first, size_t n) {
+  CtxLock lock__(ctx, true);
+  if (n == 0) return AFX_OK;
+  AFX_HIP(hipSetDevice(ctx->device));
+  const afx_show_group& G = *J.g;
+  const afx_credentials_soa& cr = G.creds;
+  const afx_shape& sh = J.sh;
+  const uint32_t na = sh.n_attributes, nr = sh.n_responses, nsp = sh.n_enc_proofs, cells = J.cells;
+  const bool kp = G.keypairs && nsp;
+  const uint32_t r_x = 1 + nr, r_cy = r_x + 3, r_enc = r_cy + na, rows = r_enc + 14 * nsp, r_val = (rows + 7) & ~7u;   // (r_val * dn * 32: a multiple of 256)
+  std::vector<uint32_t> map;
+  for (uint32_t r = 0; r < r_enc; r++) map.push_back(r);
+  for (uint32_t i = 0; i < na; i++)
+    if (sh.kinds[i] == AFX_ENC_PUBLIC_SCALAR || sh.kinds[i] == AFX_ENC_PUBLIC_POINT) map.push_back(r_val + i);
+  for (uint32_t r = r_enc; r < rows; r++) map.push_back(r);
+  if (map.size() != cells) { set_error("internal: show wire cell map"); return AFX_E_BAD_ARGS; }
+  struct { uint32_t n; uint8_t kinds[AFX_MAX_ATTRIBUTES]; } jd;   // what makes two calls one pass (statements.hpp host_pipe)
+  memset(&jd, 0, sizeof jd);
+  jd.n = na; memcpy(jd.kinds, cr.kinds, na);
+  const PlanKey jkey = plan_key("SW", &jd, sizeof jd, mode_flags(ctx) | (kp ? (uint64_t)1 << 63 : 0));
+  const size_t total = G.count;
+  return host_pipe(ctx, n, [&](Stager& st, size_t off, size_t sn) -> int {
+    const size_t f0 = first + off;
+    st.layout_tag = 3;
+    const size_t dn = st.dev_items(sn);
+    auto in = [&](const uint8_t* p, size_t k, size_t elem) { return st.add_rows(p, k, elem, total, f0, sn, dn); };
+    const size_t o_soa = st.reserve(dn * r_val * 32), o_val = in(cr.values, na, 32), o_map = st.add((const uint8_t*)map.data(), 4 * (size_t)cells);
+    const size_t o_M2 = nsp ? in(cr.M2, na, 32) : 0, o_m3 = nsp ? in(cr.m3, na, 32) : 0, o_t = in(cr.t, 1, 32), o_U = in(cr.U, 1, 32), o_V = in(cr.V, 1, 32),
+                 o_zw = in(G.rnd.z_wide, 1, 64), o_seed = in(G.rnd.rng_seed, 1, 32), o_es = nsp ? in(G.rnd.enc_seeds, nsp, 32) : 0;
+    size_t o_kp[4] = { 0, 0, 0, 0 };
+    if (kp) { o_kp[0] = in(G.keypairs->a, 1, 32); o_kp[1] = in(G.keypairs->a0, 1, 32); o_kp[2] = in(G.keypairs->a1, 1, 32); o_kp[3] = in(G.keypairs->pk, 1, 32); }
+    const size_t o_out = st.add_rows(nullptr, 1, (size_t)cells * 32, total, f0, sn, dn), o_st = st.add(nullptr, dn);
+    st.plan_fetch(J.rec, o_out, 1, (size_t)cells * 32, total, f0, sn, dn);
+    st.plan_fetch(J.status, o_st, 1, 1, total, f0, sn, dn);
+    int rc = st.upload();
+    if (rc) return rc;
+    uint8_t* soa_d = st.dev(o_soa);
+    if (st.dev(o_val) != soa_d + (size_t)r_val * dn * 32) { set_error("internal: value rows are not behind the show scratch"); return AFX_E_BAD_ARGS; }
+    auto rowp = [&](uint32_t r) { return soa_d + (size_t)r * dn * 32; };
+    afx_credentials_soa dc = cr;
+    dc.values = st.dev(o_val); dc.M2 = nsp ? st.dev(o_M2) : nullptr; dc.m3 = nsp ? st.dev(o_m3) : nullptr;
+    dc.t = st.dev(o_t); dc.U = st.dev(o_U); dc.V = st.dev(o_V);
+    const afx_keypairs_soa dk = { st.dev(o_kp[0]), st.dev(o_kp[1]), st.dev(o_kp[2]), st.dev(o_kp[3]) };
+    const afx_show_randomness dr = { st.dev(o_zw), st.dev(o_seed), nsp ? st.dev(o_es) : nullptr };
+    std::vector<afx_encproof_out> de(nsp);
+    for (uint32_t e = 0; e < nsp; e++) {
+      const uint32_t r = r_enc + 14 * e;
+      de[e] = { rowp(r), rowp(r + 1), rowp(r + 7), rowp(r + 8), rowp(r + 9), rowp(r + 10), rowp(r + 11), rowp(r + 12), rowp(r + 13) };
+    }
+    // (attr_values == null: the revealed values are not copied - their cells read the value rows)
+    const afx_presentation_out dout = { rowp(0), rowp(1), rowp(r_x), rowp(r_x + 1), rowp(r_x + 2), rowp(r_cy), nullptr, nsp ? de.data() : nullptr };
+    afx_shape shape_dev;
+    if ((rc = afx_show_dev(ctx, &dc, kp ? &dk : nullptr, &dr, dn, &dout, &shape_dev, st.dev(o_st)))) return rc;
+    if (!st.app) {   // (a call that took item slots of an earlier call's pass: that call's transposition covers them)
+      hipStream_t strm = st.stream();
+      uint8_t* out_d = st.dev(o_out);
+      const uint32_t* map_d = (const uint32_t*)st.dev(o_map);
+      const uint8_t* st_d = st.dev(o_st);
+      const uint32_t dn_ = (uint32_t)dn;
+      auto transpose = [=]() -> int { AFX_HIP(afxk_soa_to_aos(strm, soa_d, out_d, map_d, st_d, cells, dn_)); return AFX_OK; };
+      if (st.ses) st.ses->post.push_back(transpose);
+      else if ((rc = transpose())) return rc;
+    }
+    return st.fetch_all();
+  }, jkey);
+}
+
+}  // namespace
+
+extern "C" int afx_issuance_wire_section_bytes(const uint8_t* blob, size_t len, size_t* section_len_out) try {
+  if (!blob || !section_len_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  if (len < 24 || memcmp(blob, "AFXI", 4) != 0 || rd32(blob + 4) != 1) { set_error("not an AFXI v1 section"); return AFX_E_BAD_ARGS; }
+  const uint64_t count = rd32(blob + 8), cells = rd32(blob + 12);
+  const uint32_t n = rd32(blob + 16), nr = rd32(blob + 20);
+  if (n > AFX_MAX_ATTRIBUTES || nr > AFX_MAX_ATTRIBUTES + 5 || cells != 4 + (uint64_t)nr + n) { set_error("layout field out of range"); return AFX_E_BAD_ARGS; }
+  const uint64_t total = (uint64_t)afx_issuance_wire_header_bytes(n) + count * cells * 32;   // (< 2^32 * 2^7 * 2^5)
+  if (total > len) { set_error("section runs past the end of the blob"); return AFX_E_BAD_ARGS; }
+  *section_len_out = (size_t)total;
+  return AFX_OK;
+} catch (...) { return afx::exception_rc(); }
+
+extern "C" int afx_verify_issuances_mixed_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, uint8_t* status, size_t status_cap, size_t* count_out) try {
+  if (!ctx || !count_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  IStream S;
+  int rc = parse_issuances(blob, len, ctx->n, S);
+  if (rc) return rc;
+  *count_out = S.total;
+  if ((rc = check_issuances(S, status, status_cap))) return rc;
+  prepare_issuances(S, blob, status);
+  if ((rc = run_batches(ctx, launch_counts(S), [&](size_t b) { return verify_records(ctx, S.batches[b], 0, S.batches[b].count); }))) return rc;
+  scatter_issuances(S, status);
+  return AFX_OK;
+} catch (...) { return afx::exception_rc(); }
+
+// The same stream over a group's devices.  A stream of at most afx_ctx_set_small_batch_items issuances (member 0's) goes whole to ONE
+// member, the next in turn; a larger one has every batch split over the members (afx_shard_bounds), one host thread per member.
+extern "C" int afx_group_verify_issuances_mixed_wire(afx_group* group, const uint8_t* blob, size_t len, uint8_t* status, size_t status_cap,
+                                                     size_t* count_out) try {
+  if (!group || !count_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  const uint32_t m = afx_group_size(group);
+  if (m == 0) { set_error("empty group"); return AFX_E_BAD_ARGS; }
+  afx_ctx* c0 = afx_group_member(group, 0);
+  const uint32_t small = afx_group_small_batch_items(group);
+  IStream S;
+  int rc = parse_issuances(blob, len, c0->n, S);
+  if (rc) return rc;
+  *count_out = S.total;
+  if (m == 1 || (small && S.total <= small)) {
+    const uint32_t k = m == 1 ? 0 : members_alike(group, m) ? g_next_small.fetch_add(1, std::memory_order_relaxed) % m : 0;
+    GroupPin pin(group, k, true);
+    rc = afx_verify_issuances_mixed_wire(afx_group_member(group, k), blob, len, status, status_cap, count_out);
+    if (rc && m > 1) { const std::string why = afx_last_error(); set_error("member " + std::to_string(k) + ": " + why); }
+    return rc;
+  }
+  if ((rc = check_issuances(S, status, status_cap))) return rc;
+  prepare_issuances(S, blob, status);
+  rc = on_members(group, m, [&](afx_ctx* c, uint32_t k) -> int {
+    for (const IBatch& B : S.batches) {
+      if (B.fails) continue;
+      size_t first = 0, n = 0;
+      afx_shard_bounds(B.count, m, k, &first, &n);
+      if (n) { const int r = verify_records(c, B, first, n); if (r) return r; }
+    }
+    return AFX_OK;
+  });
+  if (rc) return rc;
+  scatter_issuances(S, status);
+  return AFX_OK;
+} catch (...) { return afx::exception_rc(); }
+
+extern "C" int afx_show_wire(afx_ctx* ctx, afx_show_group* groups, size_t n_groups, uint8_t* out, size_t out_cap, size_t* out_len, uint8_t* status,
+                             size_t status_len) try {
+  if (!ctx || !out_len) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  SPlan P;
+  int rc = plan_show(ctx, groups, n_groups, out != nullptr, P);
+  if (rc) return rc;
+  *out_len = P.out_len;
+  if (out) {
+    if (out_cap < P.out_len) { set_error("output buffer too small"); return AFX_E_BAD_ARGS; }
+    if (!status && status_len) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+    if ((rc = check_positions(groups, n_groups, status_len))) return rc;
+  }
+  for (size_t g = 0; g < n_groups; g++) groups[g].shape_out = P.jobs[g].sh;
+  if (!out) return AFX_OK;   // size query: shapes and length only
+  prepare_show(P, out, status);
+  if ((rc = run_batches(ctx, launch_counts(P), [&](size_t b) { return show_records(ctx, P.jobs[b], 0, P.jobs[b].g->count); }))) return rc;
+  scatter_show(P, status);
+  return AFX_OK;
+} catch (...) { return afx::exception_rc(); }
+
+// ... over a group's devices: every group split over the members, each writing its own record range of `out`; a request of at most
+// afx_ctx_set_small_batch_items credentials goes whole to one member, in turn.
+extern "C" int afx_group_show_wire(afx_group* group, afx_show_group* groups, size_t n_groups, uint8_t* out, size_t out_cap, size_t* out_len,
+                                   uint8_t* status, size_t status_len) try {
+  if (!group || !out_len) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  const uint32_t m = afx_group_size(group);
+  if (m == 0) { set_error("empty group"); return AFX_E_BAD_ARGS; }
+  afx_ctx* c0 = afx_group_member(group, 0);
+  const uint32_t small = afx_group_small_batch_items(group);
+  SPlan P;
+  int rc = plan_show(c0, groups, n_groups, out != nullptr, P);
+  if (rc) return rc;
+  if (!out || m == 1 || (small && P.items <= small)) {
+    const uint32_t k = (!out || m == 1) ? 0 : members_alike(group, m) ? g_next_small.fetch_add(1, std::memory_order_relaxed) % m : 0;
+    GroupPin pin(group, k, true);
+    rc = afx_show_wire(afx_group_member(group, k), groups, n_groups, out, out_cap, out_len, status, status_len);
+    if (rc && m > 1) { const std::string why = afx_last_error(); set_error("member " + std::to_string(k) + ": " + why); }
+    return rc;
+  }
+  *out_len = P.out_len;
+  if (out_cap < P.out_len) { set_error("output buffer too small"); return AFX_E_BAD_ARGS; }
+  if (!status && status_len) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  if ((rc = check_positions(groups, n_groups, status_len))) return rc;
+  for (size_t g = 0; g < n_groups; g++) groups[g].shape_out = P.jobs[g].sh;
+  prepare_show(P, out, status);
+  rc = on_members(group, m, [&](afx_ctx* c, uint32_t k) -> int {
+    for (const SJob& J : P.jobs) {
+      if (J.no_key) continue;
+      size_t first = 0, n = 0;
+      afx_shard_bounds(J.g->count, m, k, &first, &n);
+      if (n) { const int r = show_records(c, J, first, n); if (r) return r; }
+    }
+    return AFX_OK;
+  });
+  if (rc) return rc;
+  scatter_show(P, status);
+  return AFX_OK;
+} catch (...) { return afx::exception_rc(); }

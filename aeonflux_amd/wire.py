@@ -131,6 +131,58 @@ def unpack_issuances(blob):
     return kinds, c(rec[4 + nr:]), iss
 
 
+def issuance_section_bytes(blob):
+    """afx_issuance_wire_section_bytes: the length of the AFXI section at the start of blob (AfxError if its header is malformed)"""
+    import ctypes as C
+    from . import check, lib
+    n = C.c_size_t(0)
+    check(lib().afx_issuance_wire_section_bytes(blob, len(blob), C.byref(n)))
+    return n.value
+
+
+def verify_issuances_stream(ctx, blob):
+    """afx_verify_issuances_mixed_wire (afx_group_verify_issuances_mixed_wire for a Group): CredentialIssuance::verify over a stream of
+    AFXI sections, as issue_wire returns it.  Returns the status per issuance, in stream order."""
+    import ctypes as C
+    from . import check, lib
+    n = C.c_size_t(0)
+    cap = max(1, len(blob) // 128)   # a record is at least four cells
+    status = np.full(cap, 255, np.uint8)
+    fn = lib().afx_group_verify_issuances_mixed_wire if hasattr(ctx, "member") else lib().afx_verify_issuances_mixed_wire
+    check(fn(ctx.h, blob, len(blob), status.ctypes.data, cap, C.byref(n)))
+    return status[:n.value]
+
+
+def show_wire(ctx, items):
+    """afx_show_wire (afx_group_show_wire for a Group): AnonymousCredential::show into AFXP bytes.  items as for batch.show_mixed.
+    Returns (one AFXP section per item, back to back; [Shape per item]; status in the caller's order)."""
+    import ctypes as C
+    from . import ShowGroup, check, lib
+    from .batch import _positions, _show_args
+    arr = (ShowGroup * max(1, len(items)))()
+    keep, counts = [], []
+    for g, it in enumerate(items):
+        cs, kp, rnd, _, _, cnt, k = _show_args(it["kinds"], it["values"], it["t"], it["U"], it["V"], it.get("keypairs"), it["z_wide"], it["rng_seed"],
+                                               it.get("enc_seeds"), it.get("M2"), it.get("m3"), outputs=False)
+        arr[g].creds, arr[g].rnd, arr[g].count = cs, rnd, cnt
+        if kp is not None:
+            arr[g].keypairs = C.pointer(kp)
+        keep.append((k, kp))
+        counts.append(cnt)
+    pos, total = _positions(list(zip(items, counts)))
+    total = max([total] + [int(p.max()) + 1 for p in pos if p.size])
+    for g, p in enumerate(pos):
+        arr[g].positions = p.ctypes.data_as(C.POINTER(C.c_uint64))
+    fn = lib().afx_group_show_wire if hasattr(ctx, "member") else lib().afx_show_wire
+    out_len = C.c_size_t(0)
+    check(fn(ctx.h, arr, len(items), None, 0, C.byref(out_len), None, 0))
+    out = np.zeros(max(1, out_len.value), np.uint8)
+    status = np.full(max(1, total), 255, np.uint8)
+    check(fn(ctx.h, arr, len(items), out.ctypes.data, out.size, C.byref(out_len), status.ctypes.data, total))
+    shapes = [Shape.from_buffer_copy(bytes(arr[g].shape_out)) for g in range(len(items))]
+    return out[:out_len.value].tobytes(), shapes, status[:total]
+
+
 # ---- CredentialRequest batches ("AFXR" v1) and Issuer::issue over them --------------------------------
 def pack_requests(kinds, values):
     """kinds: AFX_ATTR_* per position; values [n,count,32] -> one AFXR section"""

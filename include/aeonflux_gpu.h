@@ -204,7 +204,7 @@ int afx_ctx_set_small_batch_items(afx_ctx* ctx, uint32_t items);
  * AnonymousCredential::show (src/credential.rs:37-46) likewise.  One such call costs one chain of field operations on a device
  * that is otherwise idle (0.8 ms), so calls that queue behind each other would cap a server at ~1.2 k calls/s whatever its thread
  * count.  Instead, host-pointer calls (afx_verify_presentations[_range,_wire,_wire_range], afx_issue[_range,_wire],
- * afx_verify_issuances[_range,_wire], afx_show[_range]) of at most 512 items that arrive while another call's kernels run are
+ * afx_verify_issuances[_range,_wire,_mixed_wire], afx_show[_range,_wire]) of at most 512 items that arrive while another call's kernels run are
  * COLLECTED: each stages its rows - calls of one statement, shape and mode into the free item slots of ONE pass, so 64 callers of
  * one shape are one pass of 64 items - and sleeps until the flush that carries its rows completes.  The caller that opened a
  * collection launches it as soon as the device is free, at the latest `max_wait_us` after it opened it (default 2000) or when it
@@ -427,6 +427,23 @@ int afx_issuance_wire_parse(const uint8_t* blob, size_t len, uint32_t* n_attribu
                             uint32_t* n_responses_out, size_t* count_out, size_t* records_offset_out);
 /* CredentialIssuance::verify (issuer.rs:48-57) over a serialized batch; the context needs no issuer key. */
 int afx_verify_issuances_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, uint8_t* status, size_t status_cap, size_t* count_out);
+/* Length (header + records) of the AFXI v1 section that starts at `blob`; AFX_E_BAD_ARGS if its header is malformed or it runs past `len`. */
+int afx_issuance_wire_section_bytes(const uint8_t* blob, size_t len, size_t* section_len_out);
+/* CredentialIssuance::verify over a stream of AFXI v1 sections back to back, exactly as afx_issue_wire writes them (a user context: no
+ * issuer key).  status[i] answers the i-th issuance of the stream; *count_out = their number.
+ *  - The status bytes are what afx_verify_issuances_wire gives when it is called on each section in turn, concatenated: sections whose
+ *    n_attributes is not the context's and the all-zero records afx_issue_wire writes for failed items included.
+ *  - AFX_E_BAD_ARGS, with nothing written to status, for a malformed section anywhere in the stream or status_cap below the item count.
+ *    An empty stream is AFX_OK with a count of 0.
+ *  - Sections of one (n_attributes, n_responses, kinds) are merged into one batch wherever they stand; its records go to the GPU from
+ *    where they lie in `blob`, section by section (no host copy), and are transposed there (k_aos_to_soa).  Small batches
+ *    of several layouts run as one set of launches (as afx_verify_issuances_mixed), calls of at most 512 items are collected with other
+ *    threads' calls (afx_ctx_set_coalescing), large batches go through the two lanes in slices. */
+int afx_verify_issuances_mixed_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, uint8_t* status, size_t status_cap, size_t* count_out);
+/* ... over a group's devices: every merged batch is split over the members (afx_shard_bounds); a stream of at most
+ * afx_ctx_set_small_batch_items issuances goes whole to one member, in turn.  Statuses equal afx_verify_issuances_mixed_wire's. */
+int afx_group_verify_issuances_mixed_wire(afx_group* group, const uint8_t* blob, size_t len, uint8_t* status, size_t status_cap,
+                                          size_t* count_out);
 
 /* IssuerParameters in the byte form the crate intends (C_W || I, 64 bytes; issuer.rs:155,163 - its own
  * to_bytes/from_bytes are unimplemented!(), parameters.rs:365-372): what afx_ctx_create was given, or what an
@@ -624,6 +641,28 @@ typedef struct {
 } afx_show_group;
 int afx_show_mixed(afx_ctx* ctx, afx_show_group* groups, size_t n_groups, uint8_t* status, size_t status_len);
 int afx_group_show_mixed(afx_group* group, afx_show_group* groups, size_t n_groups, uint8_t* status, size_t status_len);
+/* AnonymousCredential::show straight into AFXP bytes: what a user sends, ready for afx_verify_presentations_mixed_wire.
+ *  - groups: as for afx_show_mixed (creds, keypairs, rnd, count and positions mean what they mean there; shape_out is written), except
+ *    that each group's `out` member is NOT read: a caller may leave it zeroed.
+ *  - out: one AFXP v1 section per group, in group order, with the group's count and the shape afx_show gives its kinds; records in
+ *    the group's item order.  Statuses go through positions exactly as in afx_show_mixed.
+ *  - An item whose status is not AFX_ST_OK has a record of zeros; every other record is byte for byte what afx_show_mixed +
+ *    afx_wire_pack_presentations make of the same inputs.  A group with a SECRET_POINT attribute and keypairs == NULL gives a section of
+ *    zero records, every status AFX_ST_NO_SYMMETRIC_KEY.
+ *  - out == NULL: only *out_len and every shape_out, from the kinds on the host; no device work, rnd may be NULL.
+ *  - AFX_E_BAD_ARGS, with nothing written to out or status, for out_cap < *out_len, a bad status_len or positions (as afx_show_mixed
+ *    checks them) or any group afx_show would refuse (n_attributes 0 or above the context's n, a kind out of range, missing arrays).
+ *    The layout is checked for groups of count 0 too: their section still has a shape.
+ *  - afx_show_dev writes into the rows of one scratch region per pass, the revealed attribute values are read from the credential's
+ *    value rows, and k_soa_to_aos turns the region into AFXP records on the GPU (failed items zeroed), fetched in one piece.  Small
+ *    groups share one set of launches, calls of at most 512 items are collected with other threads' calls, large groups go through
+ *    the two lanes in slices. */
+int afx_show_wire(afx_ctx* ctx, afx_show_group* groups, size_t n_groups, uint8_t* out, size_t out_cap, size_t* out_len,
+                  uint8_t* status, size_t status_len);
+/* ... over a group's devices: every group is split over the members (afx_shard_bounds), each writing its own record range of `out`;
+ * a request of at most afx_ctx_set_small_batch_items credentials goes whole to one member, in turn.  Bytes equal afx_show_wire's. */
+int afx_group_show_wire(afx_group* group, afx_show_group* groups, size_t n_groups, uint8_t* out, size_t out_cap, size_t* out_len,
+                        uint8_t* status, size_t status_len);
 
 /* ---- setup helpers (cold path; still GPU arithmetic) ---------------------------------------- */
 
