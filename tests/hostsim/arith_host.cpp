@@ -12,6 +12,7 @@ static const char* last_violation = "";
 extern "C" void afx_bounds_violation(const char* what) { n_violations++; last_violation = what; }
 #include "../../aeonflux_amd/csrc/ge.cuh"
 #include "../../aeonflux_amd/csrc/sc.cuh"
+#include "../../aeonflux_amd/csrc/plan.h"
 
 static void load8(uint32_t w[8], const uint8_t* p) { memcpy(w, p, 32); }
 static sc sc_from(const uint8_t* p) { sc s; memcpy(s.v, p, 32); return s; }
@@ -227,6 +228,26 @@ void arith_sc_half_dbl(uint8_t half[32], uint8_t dbl[32], const uint8_t a[32]) {
 
 // signed-digit recoding used by k_msm: digits of s + bias; returns sum(d_i * radix^i) check value via the caller
 void arith_sc_bias(uint32_t out[8], const uint8_t s[32], uint32_t bias) { sc_bias(out, sc_from(s), bias); }
+
+// msm_recode's wide recodings, the three instantiations the kernels use (plan.h): bits = AFX_SECVAR_BITS (secret scalars on
+// variable bases), AFX_SEC_BITS (secret scalars on generators), AFX_POS_BITS (public scalars on generators).  out has
+// AFX_DIGIT_WORDS words, word 8 zeroed first as msm_recode does.  Returns 0 for any other width.
+int arith_sc_bias_wide(uint32_t out[AFX_DIGIT_WORDS], const uint8_t s[32], int bits) {
+  static_assert(AFX_DIGIT_WORDS == 9, "sc_bias_wide writes 9 words");
+  out[8] = 0;
+  if (bits == AFX_SECVAR_BITS) sc_bias_wide<AFX_SECVAR_BITS, AFX_SECVAR_WINDOWS>(out, sc_from(s));
+  else if (bits == AFX_SEC_BITS) sc_bias_wide<AFX_SEC_BITS, AFX_SEC_WINDOWS>(out, sc_from(s));
+  else if (bits == AFX_POS_BITS) sc_bias_wide<AFX_POS_BITS, AFX_POS_WINDOWS>(out, sc_from(s));
+  else return 0;
+  return 1;
+}
+// the recoding constants of plan.h the kernels are built with: {SECVAR bits, windows, stored entries; SEC bits, windows, entries;
+// POS bits, windows, entries; AFX_DIGIT_WORDS; AFX_TABLE_STORED (msm_add_var's 4-bit windows: multiples 1..8)}
+void arith_recoding_constants(int32_t out[11]) {
+  const int32_t v[11] = { AFX_SECVAR_BITS, AFX_SECVAR_WINDOWS, AFX_SECVAR_STORED, AFX_SEC_BITS, AFX_SEC_WINDOWS, AFX_SEC_ENTRIES,
+                          AFX_POS_BITS, AFX_POS_WINDOWS, AFX_POS_ENTRIES, AFX_DIGIT_WORDS, AFX_TABLE_STORED };
+  memcpy(out, v, sizeof v);
+}
 
 // field-operation counts (mul, sq) of the building blocks of k_msm / k_decode, measured on this build
 void arith_op_counts(uint64_t out[8][2]) {

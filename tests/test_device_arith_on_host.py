@@ -273,6 +273,109 @@ def test_signed_digit_recoding(arith):
         assert sum((((v >> (8 * j)) & 255) - 128) << (8 * j) for j in range(32)) == k
 
 
+def _recoding_constants(arith):
+    c = (C.c_int32 * 11)()
+    arith.arith_recoding_constants(c)
+    c = list(c)
+    # width -> (windows, largest digit magnitude the stored table serves); 4 bits: sc_bias fills 8 words of 4-bit windows and
+    # msm_add_var reads multiples 1 .. AFX_TABLE_STORED
+    return {c[0]: (c[1], c[2]), c[3]: (c[4], c[5] - 1), c[6]: (c[7], c[8] - 1), 4: (8 * 32 // 4, c[10])}, c[9]
+
+
+def _recode(arith, B, s, words):
+    """the digit words msm_recode writes for scalar s at width B"""
+    if B == 4:
+        out = (C.c_uint32 * 8)()
+        arith.arith_sc_bias(out, s.to_bytes(32, "little"), 0x88888888)
+        return list(out) + [0]
+    out = (C.c_uint32 * words)()
+    assert arith.arith_sc_bias_wide(out, s.to_bytes(32, "little"), B) == 1
+    return list(out)
+
+
+def _kernel_digits(B, windows, words, w):
+    """the digits as the kernels read them: one word, or two when the window straddles a word boundary (kernels.hip
+    msm_add_positional / msm_add_positional_secret / narrow_fetch; msm_add_var's 4-bit windows never straddle)"""
+    out = []
+    for j in range(windows):
+        o = B * j
+        k, sh = o >> 5, o & 31
+        assert k < words, (B, j)
+        x = w[k]
+        if sh + B > 32:
+            assert k + 1 < words, ("two-word read past the digit words", B, j)
+            x |= w[k + 1] << 32
+        out.append(((x >> sh) & ((1 << B) - 1)) - (1 << (B - 1)))
+    return out
+
+
+def _recoding_inputs(arith):
+    from tests.edge_values import all_scalars
+    edge = list(all_scalars().values())
+    half, dbl = (C.c_uint8 * 32)(), (C.c_uint8 * 32)()
+    derived = []
+    for s in edge:
+        arith.arith_sc_half_dbl(half, dbl, s.to_bytes(32, "little"))   # the scalars of halved jobs and of dbl terms
+        derived += [int.from_bytes(bytes(half), "little"), int.from_bytes(bytes(dbl), "little")]
+    r = stream(b"recoding-wide", 64 * 300)
+    rand = [int.from_bytes(r[64 * i:64 * i + 64], "little") % L for i in range(300)]
+    return edge, edge + derived + rand
+
+
+def test_every_recoding_width_sums_back_within_its_table(arith):
+    """msm_recode at every width the kernels use - 2 (AFX_SECVAR_BITS), 4, 6 (AFX_SEC_BITS), 13 (AFX_POS_BITS) - on the named edge
+    scalars, their halves and doubles (sc_half / sc_dbl, as msm_recode applies them) and 300 random ones: the digits, read as the
+    kernels read them, sum back to s; each lies in [-2^(B-1), 2^(B-1) - 1], so its entry index is at most the table's last
+    entry; no bit is set at or above B * WINDOWS; every two-word read stays inside AFX_DIGIT_WORDS"""
+    consts, words = _recoding_constants(arith)
+    assert sorted(consts) == [2, 4, 6, 13] and words == 9
+    _, scalars = _recoding_inputs(arith)
+    assert len(scalars) > 450
+    for B, (windows, stored) in consts.items():
+        lo, hi = -(1 << (B - 1)), (1 << (B - 1)) - 1
+        assert stored == 1 << (B - 1), (B, stored)          # digit -2^(B-1) reads the last stored multiple
+        assert B * windows <= 32 * words
+        bias = sum(1 << (B * j + B - 1) for j in range(windows))
+        for s in scalars:
+            assert 0 <= s < L
+            w = _recode(arith, B, s, words)
+            v = sum(x << (32 * i) for i, x in enumerate(w))
+            assert v == s + bias, (B, s)                     # no carry lost off the top word
+            assert v >> (B * windows) == 0, (B, s)
+            d = _kernel_digits(B, windows, words, w)
+            assert sum(x << (B * j) for j, x in enumerate(d)) == s, (B, s)
+            assert all(lo <= x <= hi and abs(x) <= stored for x in d), (B, s)
+    assert arith.arith_bounds_violations() == 0, arith.arith_last_violation()
+
+
+def test_edge_list_reaches_every_extreme_digit(arith):
+    """coverage of the named edge values: at each width, window 0 and a middle window see the digits -2^(B-1), 0 and
+    2^(B-1) - 1, and the top window its largest reachable digit (that of L - 1: the top digit does not decrease with s).  The
+    issuer keys of tests/edge_values.py have width-5 NAF weights 0, 1 and the maximum, 51."""
+    from tests.edge_values import NAF_MAX, edge_key, naf5, naf_weight
+    consts, words = _recoding_constants(arith)
+    edge, _ = _recoding_inputs(arith)
+    for B, (windows, _) in consts.items():
+        lo, hi = -(1 << (B - 1)), (1 << (B - 1)) - 1
+        digits = [_kernel_digits(B, windows, words, _recode(arith, B, s, words)) for s in edge]
+        mid = windows // 2
+        for j in (0, mid):
+            seen = {d[j] for d in digits}
+            assert {lo, 0, hi} <= seen, (B, j, sorted(seen))
+        top = _kernel_digits(B, windows, words, _recode(arith, B, L - 1, words))[-1]
+        assert top == max(d[-1] for d in digits), B
+        assert top >= 0 and any(d[-1] == top for d in digits)
+    key_weights = {naf_weight(s) for which in (0, 1) for s in edge_key(8, which)}
+    assert {0, 1, 51} <= key_weights, sorted(key_weights)
+    d = naf5(NAF_MAX)
+    assert set(x for x in d if x) == {-15, 15, 1} and all(d[i] == 0 for i in range(len(d)) if i % 5)
+    for s in edge + [NAF_MAX]:       # the restatement itself: digits sum back, odd, at most one nonzero in any 5 positions
+        d = naf5(s)
+        assert sum(x << i for i, x in enumerate(d)) == s
+        nz = [i for i, x in enumerate(d) if x]
+        assert all(d[i] % 2 and -15 <= d[i] <= 15 for i in nz) and all(b - a >= 5 for a, b in zip(nz, nz[1:]))
+
+
 # field multiplications / squarings per building block: the constants behind afx_plan_stats.field_mul / field_sq
 # (aeonflux_amd/csrc/engine.cpp Assembler::msm, plan.h AFX_DECODE_* / AFX_ENCODE_*) and DESIGN.md section 3
 OP_COUNTS = {"decode": (27, 257), "encode": (32, 255), "double_to_p2": (3, 4), "double_to_p3": (4, 4), "table_entry": (1, 0),
