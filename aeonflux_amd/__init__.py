@@ -101,6 +101,23 @@ class ShowGroup(C.Structure):
                 ("count", C.c_size_t), ("positions", C.POINTER(C.c_uint64))]
 
 
+class DeviceRng(C.Structure):
+    """afx_device_rng: randomness drawn on the device from a 32-byte seed (None: the library reads one from getrandom) and a stream
+    number (include/aeonflux_gpu.h "Randomness drawn on the device")"""
+    _fields_ = [("seed", C.c_char_p), ("stream", C.c_uint64)]
+
+
+DRAW_T_WIDE, DRAW_U_WIDE, DRAW_ISSUE_SEED, DRAW_Z_WIDE, DRAW_SHOW_SEED = 0, 1, 2, 3, 4
+
+
+def DRAW_ENC_SEED(j):
+    return 5 + j
+
+
+def draw_bytes(label):
+    return 64 if label in (DRAW_T_WIDE, DRAW_U_WIDE, DRAW_Z_WIDE) else 32
+
+
 class CoalescingStats(C.Structure):
     """afx_coalescing_stats: how concurrent small calls on one context were collected (afx_ctx_set_coalescing)"""
     _fields_ = [(k, C.c_uint64) for k in ("sessions", "calls", "items", "appended_calls", "max_calls", "leader_waits", "staging_ns", "launch_ns")]
@@ -234,6 +251,15 @@ def lib():
                 getattr(_LIB, name).argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
             for name in ("afx_show_wire", "afx_group_show_wire"):
                 getattr(_LIB, name).argtypes = [C.c_void_p, C.POINTER(ShowGroup), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t]
+        # (randomness drawn on the device: wire_issue.cpp / wire_user.cpp)
+        if hasattr(_LIB, "afx_rng_expand"):
+            _LIB.afx_rng_expand.argtypes = [C.c_void_p, C.POINTER(DeviceRng), C.c_uint32, C.c_size_t, C.c_size_t, C.c_void_p]
+            for name in ("afx_issue_wire_rng", "afx_group_issue_wire_rng"):
+                getattr(_LIB, name).argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(DeviceRng), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                                C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+            for name in ("afx_show_wire_rng", "afx_group_show_wire_rng"):
+                getattr(_LIB, name).argtypes = [C.c_void_p, C.POINTER(ShowGroup), C.c_size_t, C.POINTER(DeviceRng), C.c_void_p, C.c_size_t,
+                                                C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t]
         if hasattr(_LIB, "afx_issuer_keygen"):
             _LIB.afx_issuer_keygen.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p]
     return _LIB

@@ -195,6 +195,7 @@ struct afx_ctx {
     void* pin_in = nullptr;          // pinned image of a SMALL call's whole staging area: its many short input rows are gathered
     size_t pin_in_cap = 0;           // here on the host and go to HBM in one copy (statements.hpp Stager::upload); wiped on destroy
     hipEvent_t pin_in_done = nullptr;   // end of the copy that last read pin_in
+    afx::DevBuf draw_jobs;           // the k_draw rows (and seed wipes) of the lane's latest device-drawn call (statements.hpp Stager::draw)
   } lane[5];   // AFX_LANES: large calls alternate between lanes 0 and 1 (host_pipe, pipelining); the coalescer's sessions take whichever is free
   static constexpr int AFX_LANES = 5;
   bool pipelining = false;

@@ -84,3 +84,27 @@ __device__ __forceinline__ void keccak_f1600(uint64_t st[25]) {
 #pragma unroll
   for (int i = 0; i < 25; i++) st[i] = (uint64_t)a[i].lo | ((uint64_t)a[i].hi << 32);
 }
+
+// Device draws (include/aeonflux_gpu.h afx_device_rng): draw(seed, stream, index, label) = the first bytes of
+// SHAKE256("aeonflux-amd/device-rng/v1" || seed || u64le(stream) || u64le(index) || u8(label)).  The message is 75 bytes, one block
+// at SHAKE256's rate of 136: the padding goes in at byte 75 (0x1F) and byte 135 (0x80), one permutation, and the output is the
+// first lanes of the state (64 bytes at most, within the rate).  `ss`: the 40 staged bytes seed || u64le(stream) as five
+// little-endian words.  The 26-byte prefix leaves the message 2 bytes off the lane grid: lane L >= 4 holds word L - 4 of
+// seed || stream || index || label shifted by 16 bits.
+__device__ __forceinline__ void shake256_draw(uint64_t out[8], const uint64_t ss[5], uint64_t index, uint32_t label) {
+  const uint64_t w[7] = { ss[0], ss[1], ss[2], ss[3], ss[4], index, (uint64_t)(label & 0xffu) };
+  uint64_t st[25];
+  st[0] = 0x78756c666e6f6561ULL;   // "aeonflux"
+  st[1] = 0x7665642f646d612dULL;   // "-amd/dev"
+  st[2] = 0x2f676e722d656369ULL;   // "ice-rng/"
+  st[3] = 0x3176ULL | (w[0] << 16);   // "v1" || seed[0..6)
+#pragma unroll
+  for (int l = 4; l < 10; l++) st[l] = (w[l - 3] << 16) | (w[l - 4] >> 48);
+  st[9] |= 0x1FULL << 24;          // byte 75: SHAKE's domain bits and the first padding bit
+#pragma unroll
+  for (int l = 10; l < 25; l++) st[l] = 0;
+  st[16] = 0x80ULL << 56;          // byte 135: the last padding bit of the block
+  keccak_f1600(st);
+#pragma unroll
+  for (int l = 0; l < 8; l++) out[l] = st[l];
+}

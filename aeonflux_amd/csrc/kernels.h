@@ -52,3 +52,5 @@ hipError_t afxk_validate(hipStream_t s, const uint8_t* enc, uint8_t* ok, uint8_t
 hipError_t afxk_aos_to_soa(hipStream_t s, const uint8_t* rec, uint8_t* soa, const uint32_t* row_of_cell, uint32_t cells, uint32_t count);
 // the inverse (records of a serialized response); items whose status_dev byte is not 0 get records of zeros (status_dev may be null)
 hipError_t afxk_soa_to_aos(hipStream_t s, const uint8_t* soa, uint8_t* rec, const uint32_t* row_of_cell, const uint8_t* status_dev, uint32_t cells, uint32_t count);
+// device draws: grid row r fills jobs[r] (a device array; plan.h afx_draw_job); `max_count` = the largest count among them
+hipError_t afxk_draw(hipStream_t s, const afx_draw_job* jobs, uint32_t njobs, uint32_t max_count);

@@ -1802,6 +1802,28 @@ __global__ void __launch_bounds__(AFX_BLOCK) k_soa_to_aos(const uint8_t* __restr
   dst[1] = b;
 }
 
+// device draws (include/aeonflux_gpu.h afx_device_rng): one lane per (item, label) draw, one permutation each, written straight into
+// the row its consumer reads (k_reduce_wide / k_from_uniform, k_hash).  No LDS, no scratch: the state stays in registers.
+__global__ void __launch_bounds__(AFX_BLOCK) k_draw(const afx_draw_job* __restrict__ jobs, const afx_row* __restrict__ rows) {
+  const afx_draw_job job = *row_job(jobs, rows);
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= job.count) return;
+  const uint2* sp = reinterpret_cast<const uint2*>(job.seed);
+  uint64_t ss[5];
+#pragma unroll
+  for (int k = 0; k < 5; k++) { const uint2 v = sp[k]; ss[k] = (uint64_t)v.x | ((uint64_t)v.y << 32); }
+  uint64_t d[8];
+  shake256_draw(d, ss, job.index + i, job.label);
+  const uint32_t len = AFX_DRAW_LEN(job.label);
+  uint4* out = reinterpret_cast<uint4*>(job.dst + (uint64_t)i * len);
+  out[0] = make_uint4((uint32_t)d[0], (uint32_t)(d[0] >> 32), (uint32_t)d[1], (uint32_t)(d[1] >> 32));
+  out[1] = make_uint4((uint32_t)d[2], (uint32_t)(d[2] >> 32), (uint32_t)d[3], (uint32_t)(d[3] >> 32));
+  if (len == 64) {
+    out[2] = make_uint4((uint32_t)d[4], (uint32_t)(d[4] >> 32), (uint32_t)d[5], (uint32_t)(d[5] >> 32));
+    out[3] = make_uint4((uint32_t)d[6], (uint32_t)(d[6] >> 32), (uint32_t)d[7], (uint32_t)(d[7] >> 32));
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // host-callable launch wrappers (engine.cpp is plain C++ and never sees a kernel symbol)
 // ---------------------------------------------------------------------------------------------
@@ -2006,5 +2028,10 @@ hipError_t afxk_soa_to_aos(hipStream_t s, const uint8_t* soa, uint8_t* rec, cons
   const uint64_t n = (uint64_t)cells * count;
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_soa_to_aos, dim3((uint32_t)((n + AFX_BLOCK - 1) / AFX_BLOCK)), dim3(AFX_BLOCK), 0, s, soa, rec, row_of_cell, status, cells, count);
+  return hipGetLastError();
+}
+hipError_t afxk_draw(hipStream_t s, const afx_draw_job* jobs, uint32_t njobs, uint32_t max_count) {
+  if (!njobs || !max_count) return hipSuccess;
+  hipLaunchKernelGGL(k_draw, dim3((max_count + AFX_BLOCK - 1) / AFX_BLOCK, njobs), dim3(AFX_BLOCK), 0, s, jobs, (const afx_row*)nullptr);
   return hipGetLastError();
 }

@@ -113,6 +113,11 @@ typedef struct { uint32_t* p; uint32_t v, n; } afx_fill_job;                    
 typedef struct { const uint32_t* bad; uint8_t* status; uint32_t count, fail_code; } afx_finish_job;     /* status[i] = bad[i] ? code : 0 */
 typedef struct { const uint8_t* wide; uint8_t* out_enc; int32_t* out_var; } afx_uniform_job;            /* RistrettoPoint::from_uniform_bytes */
 typedef struct { const uint8_t* wide; uint8_t* out; } afx_reduce_job;                                   /* Scalar::from_bytes_mod_order_wide  */
+/* k_draw, one grid row per job: item i of the row gets draw(seed, stream, index + i, label) (keccak.cuh shake256_draw), AFX_DRAW_LEN(label)
+ * bytes at dst + i * AFX_DRAW_LEN(label).  `seed`: the call's 40 staged bytes seed || u64le(stream), 8-byte aligned; dst 16-byte aligned. */
+typedef struct { const uint8_t* seed; uint8_t* dst; uint64_t index; uint32_t count, label; } afx_draw_job;
+/* bytes of one draw: t_wide, U_wide and z_wide are 64 (include/aeonflux_gpu.h AFX_DRAW_*), the seeds 32 */
+#define AFX_DRAW_LEN(label) (((label) == 0u || (label) == 1u || (label) == 3u) ? 64u : 32u)
 
 /* variable point storage: struct-of-arrays, limb (c*9+l) of item i at base[(c*9+l)*count + i] */
 typedef int32_t* afx_var_t;

@@ -4,6 +4,7 @@
 #include <ctype.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include "kernels.h"
 #include "statements.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -239,7 +240,69 @@ static int ensure_pinned(void*& buf, size_t& cap, size_t bytes, size_t granule) 
   return AFX_OK;
 }
 
+// (a weak reference: the host simulation builds of the engine link the launchers they need from tests/hostsim, and their calls never
+// draw unless one of them brings this one - tests/hostsim/fake_draw.cpp)
+hipError_t afxk_draw(hipStream_t s, const afx_draw_job* jobs, uint32_t njobs, uint32_t max_count) __attribute__((weak));
+
+// k_draw over `jobs`, then k_fill_u32 zeroes the staged seeds that `wipes` name - also when the draws could not be launched.  The rows
+// go to the lane's draw_jobs buffer from `img`, which the caller keeps until the lane has been waited for.
+static int run_draws(afx_ctx* c, int lane, const std::vector<afx_draw_job>& jobs, const std::vector<afx_fill_job>& wipes, std::vector<uint8_t>& img) {
+  if (jobs.empty() && wipes.empty()) return AFX_OK;
+  if (!afxk_draw) { set_error("device draws: no k_draw launcher in this build"); return AFX_E_NO_DEVICE; }
+  afx_ctx::Lane& L = c->lane[lane];
+  const size_t jb = jobs.size() * sizeof(afx_draw_job), wb = wipes.size() * sizeof(afx_fill_job);
+  img.resize(jb + wb);
+  if (jb) memcpy(img.data(), jobs.data(), jb);
+  if (wb) memcpy(img.data() + jb, wipes.data(), wb);
+  int rc = L.draw_jobs.ensure(jb + wb);
+  if (rc) return rc;
+  AFX_HIP(hipMemcpyAsync(L.draw_jobs.p, img.data(), jb + wb, hipMemcpyHostToDevice, L.stream));
+  uint32_t max_count = 0;
+  for (const afx_draw_job& j : jobs) max_count = std::max(max_count, j.count);
+  const hipError_t e = afxk_draw(L.stream, (const afx_draw_job*)L.draw_jobs.p, (uint32_t)jobs.size(), max_count);
+  if (!wipes.empty()) AFX_HIP(afxk_fill_u32(L.stream, (const afx_fill_job*)((const uint8_t*)L.draw_jobs.p + jb), (uint32_t)wipes.size(), nullptr, 10));
+  AFX_HIP(e);
+  return AFX_OK;
+}
+
+Stager::~Stager() {
+  if (!seed_pins_.empty()) {   // (a call that failed after its upload included)
+    afx_ctx::Lane& L = c->lane[ln];
+    if (L.pin_in_done) (void)hipEventSynchronize(L.pin_in_done);   // the copy that read them
+    for (uint8_t* p : seed_pins_) afx_wipe(p, 40);
+  }
+  c->force_lane = prev_force;
+  c->cur_stager = prev_stager;
+}
+
 int Stager::upload() {
+  int rc = upload_rows();
+  if (!rc && !draws.empty()) rc = launch_draws();
+  return rc;
+}
+
+// the recorded draws with device addresses: launched now on the lane (after the rows' copy, before anything the call launches), or
+// left with the session, which launches every call's draws in one k_draw
+int Stager::launch_draws() {
+  std::vector<afx_draw_job> jobs;
+  std::vector<afx_fill_job> wipes;
+  for (const Draw& d : draws) {
+    jobs.push_back({ dev(d.seed_at), dev(d.dst_off), d.index, d.count, d.label });
+    uint32_t* s = (uint32_t*)dev(d.seed_at);
+    bool seen = false;
+    for (const afx_fill_job& w : wipes) seen |= w.p == s;
+    if (!seen) wipes.push_back({ s, 0u, 10u });
+  }
+  draws.clear();
+  if (ses) {
+    ses->draws.insert(ses->draws.end(), jobs.begin(), jobs.end());
+    ses->seed_wipes.insert(ses->seed_wipes.end(), wipes.begin(), wipes.end());
+    return AFX_OK;
+  }
+  return run_draws(c, ln, jobs, wipes, draw_rows_);
+}
+
+int Stager::upload_rows() {
   afx_ctx::Lane& L = c->lane[ln];
   if (ses && app) {
     // item slots of an existing group: nothing is written before the call is known to fit them
@@ -251,6 +314,8 @@ int Stager::upload() {
       if (k.constant && memcmp(img + k.off, k.src, k.len) != 0) return afx::AFX_RETRY_NOAPPEND;
     for (const Copy& k : copies)
       if (!k.constant) memcpy(img + k.off, k.src, k.len);
+    for (const Copy& k : copies)
+      if (k.secret) ses->seed_pins.push_back(img + k.off);   // (zeroed when the session completes or is dropped)
     uploaded = true;
     return AFX_OK;
   }
@@ -271,6 +336,8 @@ int Stager::upload() {
     uint8_t* img = (uint8_t*)L.pin_in + in_at;
     memset(img, 0, in_bytes);
     for (const Copy& k : copies) memcpy(img + k.off, k.src, k.len);
+    for (const Copy& k : copies)
+      if (k.secret) ses->seed_pins.push_back(img + k.off);
     uploaded = true;
     return AFX_OK;
   }
@@ -291,6 +358,8 @@ int Stager::upload() {
     // carry an EARLIER call's bytes (staged keys, seeds) into this call's staging area (at most 4 MB: ~50 us)
     memset(img, 0, in_bytes);
     for (const Copy& k : copies) memcpy(img + k.off, k.src, k.len);
+    for (const Copy& k : copies)
+      if (k.secret) seed_pins_.push_back(img + k.off);
     AFX_HIP(hipMemcpyAsync(L.staging.p, img, in_bytes, hipMemcpyHostToDevice, L.stream));
     AFX_HIP(hipEventRecord(L.pin_in_done, L.stream));
     return AFX_OK;
@@ -327,6 +396,7 @@ int Stager::upload() {
       if (k.off > covered) memset(img + runs[ri].img + (covered - runs[ri].off), 0, k.off - covered);
       covered = std::max(covered, k.off + k.len);
       afx::CopyPool::cut(pieces, img + runs[ri].img + (k.off - runs[ri].off), k.src, k.len);
+      if (k.secret) seed_pins_.push_back(img + runs[ri].img + (k.off - runs[ri].off));
     }
     c->copy_pool->run(std::move(pieces));
     for (const Run& r : runs) AFX_HIP(hipMemcpyAsync((uint8_t*)L.staging.p + r.off, img + r.img, r.len, hipMemcpyHostToDevice, L.stream));
@@ -711,6 +781,7 @@ int afx::Session::launch() {
   int rc = AFX_OK;
   if (in_used) AFX_HIP(hipMemcpyAsync(L.staging.p, L.pin_in, in_used, hipMemcpyHostToDevice, s));
   if (out_used) AFX_HIP(hipMemsetAsync(L.staging_out.p, 0, out_used, s));
+  if ((rc = run_draws(c, lane, draws, seed_wipes, draw_rows))) return rc;   // (before every consumer; the staged seeds are zeroed behind them)
   for (auto& f : pre)
     if ((rc = f())) break;
   if (!rc && !plans.empty()) {

@@ -262,6 +262,7 @@ extern "C" void afx_ctx_destroy(afx_ctx* c) {
   for (auto& L : c->lane) {
     L.staging.release(true);
     L.staging_out.release(true);
+    L.draw_jobs.release(true);
     if (L.pin) { memset(L.pin, 0, L.pin_cap); (void)hipHostFree(L.pin); L.pin = nullptr; L.pin_cap = 0; }
     if (L.pin_in) { memset(L.pin_in, 0, L.pin_in_cap); (void)hipHostFree(L.pin_in); L.pin_in = nullptr; L.pin_in_cap = 0; }
     if (L.pin_in_done) { (void)hipEventDestroy(L.pin_in_done); L.pin_in_done = nullptr; }

@@ -1,7 +1,9 @@
 // Helpers shared by the statement translation units (statements.cpp: context + verification,
 // statements_prove.cpp: issuance and presentation provers).
 #pragma once
+#include <errno.h>
 #include <string.h>
+#include <sys/random.h>
 #include <algorithm>
 #include <functional>
 #include <memory>
@@ -18,6 +20,8 @@ static constexpr size_t BLOB_CAP = size_t(4) << 20;   // initial size of a lane'
 static constexpr uint32_t CHUNK_DEFAULT = 1u << 19;
 // assembled plans kept for reuse (afx_ctx.plan_cache): entries / bytes
 static constexpr size_t PLAN_CACHE_ENTRIES = 512, PLAN_CACHE_BYTES = size_t(64) << 20;
+// a memset the compiler may not drop: secrets (the seeds of device draws) about to go out of use
+inline void afx_wipe(void* p, size_t n) { volatile uint8_t* v = (volatile uint8_t*)p; while (n--) *v++ = 0; }
 }
 using namespace afx;
 struct Stager;
@@ -85,13 +89,24 @@ struct Session {
   std::vector<Out> outs;
   std::vector<std::function<int()>> pre;            // launches that run after the upload and before the plans (k_aos_to_soa of a serialized batch)
   std::vector<std::function<int()>> post;           // launches that run after the plans and before the download (k_soa_to_aos of a serialized response)
+  // device draws of the calls it carries (Stager::draw): ONE k_draw launch after the upload, then the staged seeds are zeroed on the
+  // device (k_fill_u32) and, once the session completes, in the pinned image (`seed_pins`)
+  std::vector<afx_draw_job> draws;
+  std::vector<afx_fill_job> seed_wipes;
+  std::vector<uint8_t*> seed_pins;
+  std::vector<uint8_t> draw_rows;                   // the host image of draws + seed_wipes, alive until complete()
   // `shared`: a session of the context's coalescer (afx_ctx::co) - it is the context's `session` only while one call stages into it
   explicit Session(afx_ctx* ctx, bool shared_ = false) : c(ctx), shared(shared_) { if (!shared) c->session = this; }
-  ~Session() { if (!shared && c->session == this) c->session = nullptr; }   // (a shared session's last owner may be a caller that no longer holds the context)
+  ~Session() { wipe_seeds(); if (!shared && c->session == this) c->session = nullptr; }   // (a shared session's last owner may be a caller that no longer holds the context)
   Session(const Session&) = delete;
   Session& operator=(const Session&) = delete;
-  bool empty() const { return plans.empty() && outs.empty() && pre.empty() && post.empty() && in_used == 0 && out_used == 0; }
-  void drop() { plans.clear(); outs.clear(); pre.clear(); post.clear(); slots.clear(); in_used = out_used = 0; }
+  bool empty() const { return plans.empty() && outs.empty() && pre.empty() && post.empty() && draws.empty() && in_used == 0 && out_used == 0; }
+  void wipe_seeds() { for (uint8_t* p : seed_pins) afx_wipe(p, 40); seed_pins.clear(); }
+  void drop() {
+    wipe_seeds();
+    plans.clear(); outs.clear(); pre.clear(); post.clear(); slots.clear(); draws.clear(); seed_wipes.clear(); draw_rows.clear();
+    in_used = out_used = 0;
+  }
   int ensure_images(size_t in_bytes, size_t out_bytes);   // device staging + pinned images of at least these sizes (only while empty)
   // flush() = launch() + complete(): everything is enqueued on the lane's stream by launch() (the context's host state is used:
   // under afx_ctx::mu), complete() waits for the stream and scatters the results (no context state: the coalescer runs it unlocked)
@@ -105,7 +120,8 @@ struct Session {
   // the SAME arrays and declares its results there: no second plan, no second set of rows in the launches.  `ops` is the
   // layout the creating call's Stager recorded; a joining call must reproduce it operation by operation (else it is staged as a
   // group of its own).
-  struct Op { uint8_t kind; size_t rows, elem, dn, len, off; };   // kind: 0 constant bytes, 1 output bytes, 2 scratch, 3 input rows, 4 output rows
+  // kind: 0 constant bytes, 1 output bytes, 2 scratch, 3 input rows, 4 output rows, 5 device-drawn input rows (Stager::add_drawn)
+  struct Op { uint8_t kind; size_t rows, elem, dn, len, off; };
   struct Slots { PlanKey key; std::vector<Op> ops; size_t in_at, out_at, in_bytes, out_bytes; uint32_t dn, used; };
   std::vector<Slots> slots;
   // ---- coalescer state (under afx_ctx::mu) ---------------------------------------------------------------------------------
@@ -265,7 +281,7 @@ struct Stager {
   size_t in_at = 0, out_at = 0;      // session mode: where this call's regions start inside the lane's buffers
   bool uploaded = false;
   static constexpr size_t OUT = size_t(1) << 62;
-  struct Copy { size_t off; const uint8_t* src; size_t len; bool constant; };
+  struct Copy { size_t off; const uint8_t* src; size_t len; bool constant; bool secret = false; };   // secret: a staged seed (add_seed)
   struct Out { uint8_t* dst; size_t pin_off, len; };
   std::vector<Copy> copies, zeros;   // zeros: row tails of padded passes (only the unpacked upload needs them spelled out)
   std::vector<Out> outs;
@@ -285,7 +301,7 @@ struct Stager {
     c->force_lane = ln;
     c->cur_stager = this;
   }
-  ~Stager() { c->force_lane = prev_force; c->cur_stager = prev_stager; }
+  ~Stager();
   Stager(const Stager&) = delete;
   Stager& operator=(const Stager&) = delete;
   hipStream_t stream() const { return c->lane[ln].stream; }
@@ -375,6 +391,49 @@ struct Stager {
     }
     return off;
   }
+  // ---- device draws (include/aeonflux_gpu.h afx_device_rng) ----
+  // The call's 40 bytes seed || u64le(stream), staged as a one-row [dn][40] input array whose item `slot` holds them (so that a call that
+  // joins another call's item slots brings its own seed); returns where they lie.  Zeroed in the pinned image and on the device once
+  // the draws have read them.
+  size_t add_seed(const uint8_t* seed40, size_t dn) {
+    const size_t k0 = copies.size();
+    const size_t off = add_rows(seed40, 1, 40, 1, 0, 1, dn);
+    for (size_t k = k0; k < copies.size(); k++) copies[k].secret = true;
+    return off + (app ? slot : 0) * 40;
+  }
+  // items [first, first + n) of `count` at dst_off (an input or output array of `len`-byte items, len = AFX_DRAW_LEN(label)) are
+  // draw(seed at seed_at, stream, index + i, label): recorded here, launched after the upload (a session: in its merged launch set)
+  struct Draw { size_t seed_at, dst_off; uint64_t index; uint32_t count, label; };
+  std::vector<Draw> draws;
+  void draw(size_t seed_at, size_t dst_off, uint32_t label, uint64_t index, size_t count) {
+    if (count) draws.push_back({ seed_at, dst_off, index, (uint32_t)count, label });
+  }
+  // add_rows() of `rows` input rows that are not copied from the host but drawn on the device, row r with label label0 + r: items
+  // [first, first + n) of a batch whose piece k (items [first_k, first_k + n_k)) draws at indices index_k, index_k + 1, ... - one
+  // draw per piece and row
+  struct DrawPiece { size_t first, n; uint64_t index; };
+  size_t add_drawn(size_t seed_at, uint32_t label0, size_t rows, const std::vector<DrawPiece>& pieces, size_t first, size_t n, size_t dn) {
+    if (dn < n) dn = n;
+    const size_t elem = AFX_DRAW_LEN(label0);
+    size_t off;
+    if (app) {
+      off = joined(5, rows, elem, dn, 0);
+      if (mismatch) return off;
+    } else {
+      off = (in_bytes + 255) & ~size_t(255);
+      in_bytes = off + rows * dn * elem;
+      for (size_t r = 0; r < rows; r++)
+        if (dn > n) zeros.push_back({ off + (r * dn + n) * elem, nullptr, (dn - n) * elem, false });   // the padding lanes read zeros
+      ops.push_back({ 5, rows, elem, dn, 0, off });
+    }
+    const size_t s0 = app ? slot : 0;
+    for (const DrawPiece& p : pieces) {
+      const size_t lo = std::max(first, p.first), hi = std::min(first + n, p.first + p.n);
+      if (lo < hi)
+        for (size_t r = 0; r < rows; r++) draw(seed_at, off + (r * dn + s0 + lo - first) * elem, label0 + (uint32_t)r, p.index + (lo - p.first), hi - lo);
+    }
+    return off;
+  }
   uint8_t* in_base() const { return (uint8_t*)c->lane[ln].staging.p + in_at; }
   uint8_t* out_base() const { return (uint8_t*)c->lane[ln].staging_out.p + out_at; }
   uint8_t* dev(size_t off) const { return (off & OUT) ? out_base() + (off & ~OUT) : in_base() + off; }
@@ -384,7 +443,7 @@ struct Stager {
   // call at a limit of 4 / 16 / 64 MB: 2^11 items 2.73 / 2.04 / 2.03, 2^12 4.19 / 3.51 / 3.54, 2^13 and beyond no gain).
   static constexpr size_t PACK_LIMIT = size_t(16) << 20;
   static size_t pack_limit();
-  int upload();
+  int upload();                      // upload_rows() and then the recorded draws (launch_draws)
   // results: the device array [rows][dn][elem] at `off` goes to items [first, first + n) of the host array [rows][total][elem].
   // plan_fetch() declares them; fetch_all() enqueues the copies into the pinned buffer after the kernels; drain() waits for the
   // lane and scatters them to the caller's arrays.
@@ -403,6 +462,33 @@ struct Stager {
   std::vector<Pend> pend_;
   bool whole_ = false;   // fetch_all copied the whole output region: pin offsets are output offsets
   bool fetched_ = false; // fetch_all ran: the pinned buffer holds (or will hold, once the lane is drained) this call's results
+  std::vector<uint8_t*> seed_pins_;   // where upload_rows put staged seeds in a pinned image of its own: zeroed once the copy has read them
+  std::vector<uint8_t> draw_rows_;    // host image of the k_draw rows of a call that launches by itself
+  int upload_rows();
+  int launch_draws();
+};
+
+// The 40 bytes a device-drawn call stages (include/aeonflux_gpu.h afx_device_rng): seed || u64le(stream), the seed read from
+// getrandom(2) when the caller gives none.  Wiped when it goes out of scope.
+struct DrawSeed {
+  uint8_t b[40];
+  DrawSeed() { memset(b, 0, sizeof b); }
+  ~DrawSeed() { afx::afx_wipe(b, sizeof b); }
+  DrawSeed(const DrawSeed&) = delete;
+  DrawSeed& operator=(const DrawSeed&) = delete;
+  int init(const afx_device_rng* rng) {
+    if (!rng) { set_error("null device rng"); return AFX_E_BAD_ARGS; }
+    if (rng->seed) memcpy(b, rng->seed, 32);
+    else
+      for (size_t got = 0; got < 32;) {
+        const ssize_t r = getrandom(b + got, 32 - got, 0);
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) { set_error("getrandom failed"); return AFX_E_BAD_ARGS; }
+        got += (size_t)r;
+      }
+    for (int k = 0; k < 8; k++) b[32 + k] = (uint8_t)(rng->stream >> (8 * k));
+    return AFX_OK;
+  }
 };
 
 // Items per slice of a host-pointer call: slices alternate between the two lanes, so the host-to-device copy of one

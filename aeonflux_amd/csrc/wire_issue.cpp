@@ -37,6 +37,10 @@ struct Batch {
   uint8_t* out = nullptr;                                         // [count][4 + nr + n][32]
   uint8_t* status = nullptr;                                      // [count]
   std::vector<uint8_t> rec_buf, rnd_buf, out_buf, st_buf;
+  // device-drawn randomness (afx_issue_wire_rng): the call's staged seed || stream, and per section the batch items it holds and the
+  // stream index of its first (the draws of a request depend on its index in the stream only)
+  const uint8_t* seed40 = nullptr;
+  std::vector<Stager::DrawPiece> draws;
 };
 struct Stream {
   std::vector<Section> secs;
@@ -83,10 +87,12 @@ int parse_stream(const uint8_t* blob, size_t len, uint32_t ctx_n, Stream& S) {
 }
 
 // What must hold before anything is written or launched (the size query has returned before this).
-int check_call(afx_ctx* ctx, const Stream& S, const afx_issue_randomness* rnd, size_t out_cap, const uint8_t* status, size_t status_cap) {
+// seed40: the randomness is drawn on the device (rnd is not read)
+int check_call(afx_ctx* ctx, const Stream& S, const afx_issue_randomness* rnd, const uint8_t* seed40, size_t out_cap, const uint8_t* status,
+               size_t status_cap) {
   if (out_cap < S.out_len) { set_error("output buffer too small"); return AFX_E_BAD_ARGS; }
   if (status_cap < S.total || (!status && S.total)) { set_error("status buffer too small"); return AFX_E_BAD_ARGS; }
-  if (!S.batches.empty() && (!rnd || !rnd->t_wide || !rnd->U_wide || !rnd->rng_seed)) { set_error("null randomness array"); return AFX_E_BAD_ARGS; }
+  if (!S.batches.empty() && !seed40 && (!rnd || !rnd->t_wide || !rnd->U_wide || !rnd->rng_seed)) { set_error("null randomness array"); return AFX_E_BAD_ARGS; }
   for (const Batch& B : S.batches)
     if (B.count > 0xffffffffu / 64) { set_error("too many requests of one layout"); return AFX_E_BAD_ARGS; }
   if (!ctx->has_key) { set_error("Issuer::issue needs the issuer key"); return AFX_E_NO_KEY; }
@@ -95,7 +101,7 @@ int check_call(afx_ctx* ctx, const Stream& S, const afx_issue_randomness* rnd, s
 
 // Every section's AFXI header; the sections the GPU does not see (n != the context's n, or n == 0: MacCreation, amacs.rs:285-287)
 // get records of zeros and their statuses here.  Then every batch's arrays: the caller's own, or gathered copies.
-void prepare(Stream& S, const uint8_t* blob, const afx_issue_randomness* rnd, uint32_t ctx_n, uint8_t* out, uint8_t* status) {
+void prepare(Stream& S, const uint8_t* blob, const afx_issue_randomness* rnd, const uint8_t* seed40, uint32_t ctx_n, uint8_t* out, uint8_t* status) {
   const uint32_t nr = ctx_n + 5;
   for (const Section& s : S.secs) {
     uint8_t* h = out + s.out_off;
@@ -110,16 +116,21 @@ void prepare(Stream& S, const uint8_t* blob, const afx_issue_randomness* rnd, ui
   }
   for (Batch& B : S.batches) {
     const size_t rb = (size_t)B.n * 32, ob = (size_t)(4 + nr + B.n) * 32;
+    if (seed40) {   // (no rnd_buf: the draws land in the staged rows themselves)
+      B.seed40 = seed40;
+      size_t at = 0;
+      for (size_t k : B.secs) { B.draws.push_back({ at, S.secs[k].count, (uint64_t)S.secs[k].first }); at += S.secs[k].count; }
+    }
     if (B.secs.size() == 1) {
       const Section& s = S.secs[B.secs[0]];
       B.rec = blob + s.off + s.hdr;
-      B.t_wide = rnd->t_wide + s.first * 64; B.U_wide = rnd->U_wide + s.first * 64; B.seed = rnd->rng_seed + s.first * 32;
+      if (!seed40) { B.t_wide = rnd->t_wide + s.first * 64; B.U_wide = rnd->U_wide + s.first * 64; B.seed = rnd->rng_seed + s.first * 32; }
       B.out = out + s.out_off + s.out_hdr;
       B.status = status + s.first;
       continue;
     }
     B.rec_buf.resize(B.count * rb);
-    B.rnd_buf.resize(B.count * 160);
+    if (!seed40) B.rnd_buf.resize(B.count * 160);
     B.out_buf.assign(B.count * ob, 0);
     B.st_buf.assign(B.count, AFX_ST_MAC_CREATION);
     uint8_t *tw = B.rnd_buf.data(), *uw = tw + B.count * 64, *sd = uw + B.count * 64;
@@ -127,12 +138,15 @@ void prepare(Stream& S, const uint8_t* blob, const afx_issue_randomness* rnd, ui
     for (size_t k : B.secs) {
       const Section& s = S.secs[k];
       memcpy(B.rec_buf.data() + at * rb, blob + s.off + s.hdr, s.count * rb);
-      memcpy(tw + at * 64, rnd->t_wide + s.first * 64, s.count * 64);
-      memcpy(uw + at * 64, rnd->U_wide + s.first * 64, s.count * 64);
-      memcpy(sd + at * 32, rnd->rng_seed + s.first * 32, s.count * 32);
+      if (!seed40) {
+        memcpy(tw + at * 64, rnd->t_wide + s.first * 64, s.count * 64);
+        memcpy(uw + at * 64, rnd->U_wide + s.first * 64, s.count * 64);
+        memcpy(sd + at * 32, rnd->rng_seed + s.first * 32, s.count * 32);
+      }
       at += s.count;
     }
-    B.rec = B.rec_buf.data(); B.t_wide = tw; B.U_wide = uw; B.seed = sd;
+    B.rec = B.rec_buf.data();
+    if (!seed40) { B.t_wide = tw; B.U_wide = uw; B.seed = sd; }
     B.out = B.out_buf.data(); B.status = B.st_buf.data();
   }
 }
@@ -168,16 +182,26 @@ int issue_records(afx_ctx* ctx, const Batch& B, size_t first, size_t n) {
   struct { uint32_t n; uint8_t kinds[AFX_MAX_ATTRIBUTES]; } jd;   // what makes two calls one pass (statements.hpp host_pipe)
   memset(&jd, 0, sizeof jd);
   jd.n = na; memcpy(jd.kinds, B.kinds, AFX_MAX_ATTRIBUTES);
-  const PlanKey jkey = plan_key("IW", &jd, sizeof jd, mode_flags(ctx));
+  const PlanKey jkey = plan_key(B.seed40 ? "IWR" : "IW", &jd, sizeof jd, mode_flags(ctx));
   const size_t total = B.count;
   return host_pipe(ctx, n, [&](Stager& st, size_t off, size_t sn) -> int {
     const size_t f0 = first + off;
-    st.layout_tag = 2;
+    st.layout_tag = B.seed40 ? 4 : 2;
     const size_t dn = st.dev_items(sn);
     const size_t o_rec = st.add_rows(B.rec, 1, (size_t)na * 32, total, f0, sn, dn), o_min = st.add((const uint8_t*)map_in.data(), 4 * (size_t)na),
-                 o_mout = st.add((const uint8_t*)map_out.data(), 4 * (size_t)cells), o_tw = st.add_rows(B.t_wide, 1, 64, total, f0, sn, dn),
-                 o_uw = st.add_rows(B.U_wide, 1, 64, total, f0, sn, dn), o_seed = st.add_rows(B.seed, 1, 32, total, f0, sn, dn),
-                 o_soa = st.reserve(dn * cells * 32), o_out = st.add_rows(nullptr, 1, (size_t)cells * 32, total, f0, sn, dn), o_st = st.add(nullptr, dn);
+                 o_mout = st.add((const uint8_t*)map_out.data(), 4 * (size_t)cells);
+    size_t o_tw, o_uw, o_seed;
+    if (B.seed40) {   // drawn on the device after the upload, into the rows k_reduce_wide, k_from_uniform and k_hash read
+      const size_t s_at = st.add_seed(B.seed40, dn);
+      o_tw = st.add_drawn(s_at, AFX_DRAW_T_WIDE, 1, B.draws, f0, sn, dn);
+      o_uw = st.add_drawn(s_at, AFX_DRAW_U_WIDE, 1, B.draws, f0, sn, dn);
+      o_seed = st.add_drawn(s_at, AFX_DRAW_ISSUE_SEED, 1, B.draws, f0, sn, dn);
+    } else {
+      o_tw = st.add_rows(B.t_wide, 1, 64, total, f0, sn, dn);
+      o_uw = st.add_rows(B.U_wide, 1, 64, total, f0, sn, dn);
+      o_seed = st.add_rows(B.seed, 1, 32, total, f0, sn, dn);
+    }
+    const size_t o_soa = st.reserve(dn * cells * 32), o_out = st.add_rows(nullptr, 1, (size_t)cells * 32, total, f0, sn, dn), o_st = st.add(nullptr, dn);
     st.plan_fetch(B.out, o_out, 1, (size_t)cells * 32, total, f0, sn, dn);
     st.plan_fetch(B.status, o_st, 1, 1, total, f0, sn, dn);
     int rc = st.upload();
@@ -345,8 +369,10 @@ extern "C" int afx_request_wire_pack(const afx_attributes_soa* requests, size_t 
   return AFX_OK;
 } catch (...) { return afx::exception_rc(); }
 
-extern "C" int afx_issue_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, const afx_issue_randomness* rnd, uint8_t* out, size_t out_cap, size_t* out_len,
-                              uint8_t* status, size_t status_cap, size_t* count_out) try {
+namespace {
+// afx_issue_wire (seed40 == null) and afx_issue_wire_rng (seed40: the staged seed || stream; rnd is not read)
+int issue_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, const afx_issue_randomness* rnd, const uint8_t* seed40, uint8_t* out, size_t out_cap,
+               size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out) {
   if (!ctx || !out_len || !count_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   Stream S;
   int rc = parse_stream(blob, len, ctx->n, S);
@@ -354,11 +380,37 @@ extern "C" int afx_issue_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, con
   *out_len = S.out_len;
   *count_out = S.total;
   if (!out) return AFX_OK;   // size query: headers only
-  if ((rc = check_call(ctx, S, rnd, out_cap, status, status_cap))) return rc;
-  prepare(S, blob, rnd, ctx->n, out, status);
+  if ((rc = check_call(ctx, S, rnd, seed40, out_cap, status, status_cap))) return rc;
+  prepare(S, blob, rnd, seed40, ctx->n, out, status);
   if ((rc = run_batches(ctx, S))) return rc;
   scatter(S, ctx->n, out, status);
   return AFX_OK;
+}
+int group_issue_wire(afx_group* group, const uint8_t* blob, size_t len, const afx_issue_randomness* rnd, const uint8_t* seed40, uint8_t* out,
+                     size_t out_cap, size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out);
+}  // namespace
+
+extern "C" int afx_issue_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, const afx_issue_randomness* rnd, uint8_t* out, size_t out_cap, size_t* out_len,
+                              uint8_t* status, size_t status_cap, size_t* count_out) try {
+  return issue_wire(ctx, blob, len, rnd, nullptr, out, out_cap, out_len, status, status_cap, count_out);
+} catch (...) { return afx::exception_rc(); }
+
+extern "C" int afx_issue_wire_rng(afx_ctx* ctx, const uint8_t* blob, size_t len, const afx_device_rng* rng, uint8_t* out, size_t out_cap,
+                                  size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out) try {
+  if (!rng) { set_error("null device rng"); return AFX_E_BAD_ARGS; }
+  DrawSeed seed;
+  int rc = out ? seed.init(rng) : AFX_OK;   // (the size query draws nothing)
+  if (rc) return rc;
+  return issue_wire(ctx, blob, len, nullptr, seed.b, out, out_cap, out_len, status, status_cap, count_out);
+} catch (...) { return afx::exception_rc(); }
+
+extern "C" int afx_group_issue_wire_rng(afx_group* group, const uint8_t* blob, size_t len, const afx_device_rng* rng, uint8_t* out, size_t out_cap,
+                                        size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out) try {
+  if (!rng) { set_error("null device rng"); return AFX_E_BAD_ARGS; }
+  DrawSeed seed;   // one seed for the whole group call: every member indexes by the request's ordinal in the stream
+  int rc = out ? seed.init(rng) : AFX_OK;
+  if (rc) return rc;
+  return group_issue_wire(group, blob, len, nullptr, seed.b, out, out_cap, out_len, status, status_cap, count_out);
 } catch (...) { return afx::exception_rc(); }
 
 // The same stream over a group's devices.  A stream of at most afx_ctx_set_small_batch_items requests (member 0's) goes whole to ONE
@@ -366,6 +418,12 @@ extern "C" int afx_issue_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, con
 // writing its own record range of `out`.  The headers and the MacCreation sections are written once, here.
 extern "C" int afx_group_issue_wire(afx_group* group, const uint8_t* blob, size_t len, const afx_issue_randomness* rnd, uint8_t* out, size_t out_cap,
                                     size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out) try {
+  return group_issue_wire(group, blob, len, rnd, nullptr, out, out_cap, out_len, status, status_cap, count_out);
+} catch (...) { return afx::exception_rc(); }
+
+namespace {
+int group_issue_wire(afx_group* group, const uint8_t* blob, size_t len, const afx_issue_randomness* rnd, const uint8_t* seed40, uint8_t* out,
+                     size_t out_cap, size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out) {
   if (!group || !out_len || !count_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   const uint32_t m = afx_group_size(group);
   if (m == 0) { set_error("empty group"); return AFX_E_BAD_ARGS; }
@@ -374,7 +432,7 @@ extern "C" int afx_group_issue_wire(afx_group* group, const uint8_t* blob, size_
   if (m == 1 || (small && len && [&] { Stream T; return !parse_stream(blob, len, c0->n, T) && T.total <= small; }())) {
     const uint32_t k = m == 1 ? 0 : members_alike(group, m) ? g_next_small.fetch_add(1, std::memory_order_relaxed) % m : 0;
     GroupPin pin(group, k, true);
-    const int rc = afx_issue_wire(afx_group_member(group, k), blob, len, rnd, out, out_cap, out_len, status, status_cap, count_out);
+    const int rc = issue_wire(afx_group_member(group, k), blob, len, rnd, seed40, out, out_cap, out_len, status, status_cap, count_out);
     if (rc && m > 1) { const std::string why = afx_last_error(); set_error("member " + std::to_string(k) + ": " + why); }
     return rc;
   }
@@ -384,8 +442,8 @@ extern "C" int afx_group_issue_wire(afx_group* group, const uint8_t* blob, size_
   *out_len = S.out_len;
   *count_out = S.total;
   if (!out) return AFX_OK;
-  if ((rc = check_call(c0, S, rnd, out_cap, status, status_cap))) return rc;
-  prepare(S, blob, rnd, c0->n, out, status);
+  if ((rc = check_call(c0, S, rnd, seed40, out_cap, status, status_cap))) return rc;
+  prepare(S, blob, rnd, seed40, c0->n, out, status);
   std::vector<int> rcs(m, AFX_OK);
   std::vector<std::string> errs(m);
   auto body = [&](uint32_t k) {
@@ -407,4 +465,28 @@ extern "C" int afx_group_issue_wire(afx_group* group, const uint8_t* blob, size_
     if (rcs[k]) { set_error("member " + std::to_string(k) + ": " + errs[k]); return rcs[k]; }
   scatter(S, c0->n, out, status);
   return AFX_OK;
+}
+}  // namespace
+
+// Device draws straight into a host array (include/aeonflux_gpu.h afx_rng_expand): k_draw into an output row of the staging area,
+// fetched like any result; large counts go through the two lanes in slices.
+static_assert(sizeof(size_t) == sizeof(uint64_t), "afx_rng_expand takes a 64-bit index as size_t");
+extern "C" int afx_rng_expand(afx_ctx* ctx, const afx_device_rng* rng, uint32_t label, size_t first, size_t count, uint8_t* out) try {
+  if (!ctx || !rng || (!out && count)) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  if (label > AFX_DRAW_ENC_SEED(AFX_MAX_ATTRIBUTES - 1)) { set_error("draw label out of range"); return AFX_E_BAD_ARGS; }
+  if (count == 0) return AFX_OK;
+  DrawSeed seed;
+  int rc = seed.init(rng);
+  if (rc) return rc;
+  CtxLock lock__(ctx);
+  AFX_HIP(hipSetDevice(ctx->device));
+  const size_t len = AFX_DRAW_BYTES(label);
+  return host_pipe(ctx, count, [&](Stager& st, size_t off, size_t sn) -> int {
+    const size_t dn = st.dev_items(sn);
+    const size_t s_at = st.add_seed(seed.b, dn), o_out = st.add_rows(nullptr, 1, len, count, off, sn, dn);
+    st.draw(s_at, o_out, label, first + off, sn);
+    st.plan_fetch(out, o_out, 1, len, count, off, sn, dn);
+    const int r = st.upload();
+    return r ? r : st.fetch_all();
+  });
 } catch (...) { return afx::exception_rc(); }

@@ -299,6 +299,7 @@ struct SJob {
   uint32_t cells = 0;
   size_t out_off = 0, hdr = 0;
   bool no_key = false;                 // SECRET_POINT attributes and no keypairs: NoSymmetricKey for every item, nothing launched
+  uint64_t index0 = 0;                 // draw index of the group's first item (afx_show_wire_rng): the counts of the groups before it
   uint8_t* rec = nullptr;              // out + out_off + hdr: [count][cells][32]
   uint8_t* status = nullptr;           // the caller's contiguous range, or st_buf (positions given)
   std::vector<uint8_t> st_buf;
@@ -310,7 +311,8 @@ struct SPlan {
 
 // The groups' sections and their length; every group whose layout afx_show refuses fails the call.  `arrays`: the full call also
 // checks the arrays afx_show would read (the size query reads none).
-int plan_show(afx_ctx* ctx, const afx_show_group* groups, size_t n_groups, bool arrays, SPlan& P) {
+// `drawn`: the randomness is drawn on the device (afx_show_wire_rng): the groups' rnd is not read.
+int plan_show(afx_ctx* ctx, const afx_show_group* groups, size_t n_groups, bool arrays, SPlan& P, bool drawn = false) {
   if (!groups && n_groups) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   P.jobs.resize(n_groups);
   for (size_t gi = 0; gi < n_groups; gi++) {
@@ -329,12 +331,13 @@ int plan_show(afx_ctx* ctx, const afx_show_group* groups, size_t n_groups, bool 
     const uint32_t nsp = J.sh.n_enc_proofs;
     J.no_key = nsp && !G.keypairs;
     if (arrays && G.count) {   // (afx_show_range's checks)
-      if (!cr.values || !cr.t || !cr.U || !cr.V || !G.rnd.z_wide || !G.rnd.rng_seed || (nsp && (!G.rnd.enc_seeds || !cr.M2 || !cr.m3)))
+      if (!cr.values || !cr.t || !cr.U || !cr.V || (!drawn && (!G.rnd.z_wide || !G.rnd.rng_seed)) || (nsp && ((!drawn && !G.rnd.enc_seeds) || !cr.M2 || !cr.m3)))
         return bad("null batch array");
       if (G.keypairs && nsp && (!G.keypairs->a || !G.keypairs->a0 || !G.keypairs->a1 || !G.keypairs->pk)) return bad("null keypair array");
     }
     J.out_off = P.out_len;
     P.out_len += J.hdr + G.count * J.cells * 32;   // (< 2^26 * 2^10 * 2^5 per group)
+    J.index0 = P.items;
     P.items += G.count;
   }
   return AFX_OK;
@@ -398,7 +401,9 @@ std::vector<size_t> launch_counts(const SPlan& P) {
 // and the credential's value rows are staged right behind it, so that a revealed value's cell maps to its value row directly.
 // afx_show_dev fills the rows; k_soa_to_aos copies the region out as AFXP records (right after the plan, or the session's `post`),
 // fetched in one piece.
-int show_records(afx_ctx* ctx, const SJob& J, size_t first, size_t n) {
+// seed40: the call's staged seed || stream (afx_show_wire_rng): z_wide, rng_seed and enc_seeds are drawn on the device at the items'
+// ordinals (J.index0 + i), into the rows afx_show_dev reads
+int show_records(afx_ctx* ctx, const SJob& J, size_t first, size_t n, const uint8_t* seed40 = nullptr) {
   CtxLock lock__(ctx, true);
   if (n == 0) return AFX_OK;
   AFX_HIP(hipSetDevice(ctx->device));
@@ -417,16 +422,25 @@ int show_records(afx_ctx* ctx, const SJob& J, size_t first, size_t n) {
   struct { uint32_t n; uint8_t kinds[AFX_MAX_ATTRIBUTES]; } jd;   // what makes two calls one pass (statements.hpp host_pipe)
   memset(&jd, 0, sizeof jd);
   jd.n = na; memcpy(jd.kinds, cr.kinds, na);
-  const PlanKey jkey = plan_key("SW", &jd, sizeof jd, mode_flags(ctx) | (kp ? (uint64_t)1 << 63 : 0));
+  const PlanKey jkey = plan_key(seed40 ? "SWR" : "SW", &jd, sizeof jd, mode_flags(ctx) | (kp ? (uint64_t)1 << 63 : 0));
+  const std::vector<Stager::DrawPiece> draws = { { 0, (size_t)G.count, J.index0 } };
   const size_t total = G.count;
   return host_pipe(ctx, n, [&](Stager& st, size_t off, size_t sn) -> int {
     const size_t f0 = first + off;
-    st.layout_tag = 3;
+    st.layout_tag = seed40 ? 5 : 3;
     const size_t dn = st.dev_items(sn);
     auto in = [&](const uint8_t* p, size_t k, size_t elem) { return st.add_rows(p, k, elem, total, f0, sn, dn); };
     const size_t o_soa = st.reserve(dn * r_val * 32), o_val = in(cr.values, na, 32), o_map = st.add((const uint8_t*)map.data(), 4 * (size_t)cells);
-    const size_t o_M2 = nsp ? in(cr.M2, na, 32) : 0, o_m3 = nsp ? in(cr.m3, na, 32) : 0, o_t = in(cr.t, 1, 32), o_U = in(cr.U, 1, 32), o_V = in(cr.V, 1, 32),
-                 o_zw = in(G.rnd.z_wide, 1, 64), o_seed = in(G.rnd.rng_seed, 1, 32), o_es = nsp ? in(G.rnd.enc_seeds, nsp, 32) : 0;
+    const size_t o_M2 = nsp ? in(cr.M2, na, 32) : 0, o_m3 = nsp ? in(cr.m3, na, 32) : 0, o_t = in(cr.t, 1, 32), o_U = in(cr.U, 1, 32), o_V = in(cr.V, 1, 32);
+    size_t o_zw, o_seed, o_es = 0;
+    if (seed40) {
+      const size_t s_at = st.add_seed(seed40, dn);
+      o_zw = st.add_drawn(s_at, AFX_DRAW_Z_WIDE, 1, draws, f0, sn, dn);
+      o_seed = st.add_drawn(s_at, AFX_DRAW_SHOW_SEED, 1, draws, f0, sn, dn);
+      if (nsp) o_es = st.add_drawn(s_at, AFX_DRAW_ENC_SEED(0), nsp, draws, f0, sn, dn);
+    } else {
+      o_zw = in(G.rnd.z_wide, 1, 64); o_seed = in(G.rnd.rng_seed, 1, 32); o_es = nsp ? in(G.rnd.enc_seeds, nsp, 32) : 0;
+    }
     size_t o_kp[4] = { 0, 0, 0, 0 };
     if (kp) { o_kp[0] = in(G.keypairs->a, 1, 32); o_kp[1] = in(G.keypairs->a0, 1, 32); o_kp[2] = in(G.keypairs->a1, 1, 32); o_kp[3] = in(G.keypairs->pk, 1, 32); }
     const size_t o_out = st.add_rows(nullptr, 1, (size_t)cells * 32, total, f0, sn, dn), o_st = st.add(nullptr, dn);
@@ -528,11 +542,13 @@ extern "C" int afx_group_verify_issuances_mixed_wire(afx_group* group, const uin
   return AFX_OK;
 } catch (...) { return afx::exception_rc(); }
 
-extern "C" int afx_show_wire(afx_ctx* ctx, afx_show_group* groups, size_t n_groups, uint8_t* out, size_t out_cap, size_t* out_len, uint8_t* status,
-                             size_t status_len) try {
+namespace {
+// afx_show_wire (seed40 == null) and afx_show_wire_rng (seed40: the staged seed || stream; the groups' rnd is not read)
+int show_wire(afx_ctx* ctx, afx_show_group* groups, size_t n_groups, const uint8_t* seed40, uint8_t* out, size_t out_cap, size_t* out_len,
+              uint8_t* status, size_t status_len) {
   if (!ctx || !out_len) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   SPlan P;
-  int rc = plan_show(ctx, groups, n_groups, out != nullptr, P);
+  int rc = plan_show(ctx, groups, n_groups, out != nullptr, P, seed40 != nullptr);
   if (rc) return rc;
   *out_len = P.out_len;
   if (out) {
@@ -543,27 +559,59 @@ extern "C" int afx_show_wire(afx_ctx* ctx, afx_show_group* groups, size_t n_grou
   for (size_t g = 0; g < n_groups; g++) groups[g].shape_out = P.jobs[g].sh;
   if (!out) return AFX_OK;   // size query: shapes and length only
   prepare_show(P, out, status);
-  if ((rc = run_batches(ctx, launch_counts(P), [&](size_t b) { return show_records(ctx, P.jobs[b], 0, P.jobs[b].g->count); }))) return rc;
+  if ((rc = run_batches(ctx, launch_counts(P), [&](size_t b) { return show_records(ctx, P.jobs[b], 0, P.jobs[b].g->count, seed40); }))) return rc;
   scatter_show(P, status);
   return AFX_OK;
+}
+int group_show_wire(afx_group* group, afx_show_group* groups, size_t n_groups, const uint8_t* seed40, uint8_t* out, size_t out_cap,
+                    size_t* out_len, uint8_t* status, size_t status_len);
+}  // namespace
+
+extern "C" int afx_show_wire(afx_ctx* ctx, afx_show_group* groups, size_t n_groups, uint8_t* out, size_t out_cap, size_t* out_len, uint8_t* status,
+                             size_t status_len) try {
+  return show_wire(ctx, groups, n_groups, nullptr, out, out_cap, out_len, status, status_len);
+} catch (...) { return afx::exception_rc(); }
+
+extern "C" int afx_show_wire_rng(afx_ctx* ctx, afx_show_group* groups, size_t n_groups, const afx_device_rng* rng, uint8_t* out, size_t out_cap,
+                                 size_t* out_len, uint8_t* status, size_t status_len) try {
+  if (!rng) { set_error("null device rng"); return AFX_E_BAD_ARGS; }
+  DrawSeed seed;
+  int rc = out ? seed.init(rng) : AFX_OK;   // (the size query draws nothing)
+  if (rc) return rc;
+  return show_wire(ctx, groups, n_groups, seed.b, out, out_cap, out_len, status, status_len);
+} catch (...) { return afx::exception_rc(); }
+
+extern "C" int afx_group_show_wire_rng(afx_group* group, afx_show_group* groups, size_t n_groups, const afx_device_rng* rng, uint8_t* out,
+                                       size_t out_cap, size_t* out_len, uint8_t* status, size_t status_len) try {
+  if (!rng) { set_error("null device rng"); return AFX_E_BAD_ARGS; }
+  DrawSeed seed;   // one seed for the whole group call: every member indexes by the credential's ordinal over the groups
+  int rc = out ? seed.init(rng) : AFX_OK;
+  if (rc) return rc;
+  return group_show_wire(group, groups, n_groups, seed.b, out, out_cap, out_len, status, status_len);
 } catch (...) { return afx::exception_rc(); }
 
 // ... over a group's devices: every group split over the members, each writing its own record range of `out`; a request of at most
 // afx_ctx_set_small_batch_items credentials goes whole to one member, in turn.
 extern "C" int afx_group_show_wire(afx_group* group, afx_show_group* groups, size_t n_groups, uint8_t* out, size_t out_cap, size_t* out_len,
                                    uint8_t* status, size_t status_len) try {
+  return group_show_wire(group, groups, n_groups, nullptr, out, out_cap, out_len, status, status_len);
+} catch (...) { return afx::exception_rc(); }
+
+namespace {
+int group_show_wire(afx_group* group, afx_show_group* groups, size_t n_groups, const uint8_t* seed40, uint8_t* out, size_t out_cap,
+                    size_t* out_len, uint8_t* status, size_t status_len) {
   if (!group || !out_len) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   const uint32_t m = afx_group_size(group);
   if (m == 0) { set_error("empty group"); return AFX_E_BAD_ARGS; }
   afx_ctx* c0 = afx_group_member(group, 0);
   const uint32_t small = afx_group_small_batch_items(group);
   SPlan P;
-  int rc = plan_show(c0, groups, n_groups, out != nullptr, P);
+  int rc = plan_show(c0, groups, n_groups, out != nullptr, P, seed40 != nullptr);
   if (rc) return rc;
   if (!out || m == 1 || (small && P.items <= small)) {
     const uint32_t k = (!out || m == 1) ? 0 : members_alike(group, m) ? g_next_small.fetch_add(1, std::memory_order_relaxed) % m : 0;
     GroupPin pin(group, k, true);
-    rc = afx_show_wire(afx_group_member(group, k), groups, n_groups, out, out_cap, out_len, status, status_len);
+    rc = show_wire(afx_group_member(group, k), groups, n_groups, seed40, out, out_cap, out_len, status, status_len);
     if (rc && m > 1) { const std::string why = afx_last_error(); set_error("member " + std::to_string(k) + ": " + why); }
     return rc;
   }
@@ -578,11 +626,12 @@ extern "C" int afx_group_show_wire(afx_group* group, afx_show_group* groups, siz
       if (J.no_key) continue;
       size_t first = 0, n = 0;
       afx_shard_bounds(J.g->count, m, k, &first, &n);
-      if (n) { const int r = show_records(c, J, first, n); if (r) return r; }
+      if (n) { const int r = show_records(c, J, first, n, seed40); if (r) return r; }
     }
     return AFX_OK;
   });
   if (rc) return rc;
   scatter_show(P, status);
   return AFX_OK;
-} catch (...) { return afx::exception_rc(); }
+}
+}  // namespace

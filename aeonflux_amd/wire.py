@@ -183,6 +183,58 @@ def show_wire(ctx, items):
     return out[:out_len.value].tobytes(), shapes, status[:total]
 
 
+def _device_rng(seed, stream):
+    from . import DeviceRng
+    if seed is not None:
+        seed = bytes(seed)
+        assert len(seed) == 32, "a device-rng seed is 32 bytes"
+    return DeviceRng(seed, stream)
+
+
+def rng_expand(ctx, label, first, count, seed=None, stream=0):
+    """afx_rng_expand: draw(seed, stream, first + i, label) for i < count -> [count, AFX_DRAW_BYTES(label)] uint8 (seed None: one from
+    getrandom, which the caller never sees)"""
+    import ctypes as C
+    from . import check, draw_bytes, lib
+    out = np.zeros((max(1, count), draw_bytes(label)), np.uint8)
+    rng = _device_rng(seed, stream)
+    check(lib().afx_rng_expand(ctx.h, C.byref(rng), label, first, count, out.ctypes.data))
+    return out[:count]
+
+
+def show_wire_rng(ctx, items, seed=None, stream=0):
+    """afx_show_wire_rng (afx_group_show_wire_rng for a Group): show_wire with z_wide, rng_seed and enc_seeds drawn on the device from
+    (seed, stream) at each credential's ordinal over the items; items need no randomness arrays"""
+    import ctypes as C
+    from . import ShowGroup, check, lib
+    from .batch import _positions, _show_args
+    arr = (ShowGroup * max(1, len(items)))()
+    keep, counts = [], []
+    for g, it in enumerate(items):
+        nsp = sum(1 for k in it["kinds"] if k == 4)
+        dummy64, dummy32 = np.zeros((1, 64), np.uint8), np.zeros((1, 32), np.uint8)   # (not read)
+        cs, kp, rnd, _, _, cnt, k = _show_args(it["kinds"], it["values"], it["t"], it["U"], it["V"], it.get("keypairs"), dummy64, dummy32,
+                                               np.zeros((max(1, nsp), 1, 32), np.uint8), it.get("M2"), it.get("m3"), outputs=False)
+        arr[g].creds, arr[g].count = cs, cnt
+        if kp is not None:
+            arr[g].keypairs = C.pointer(kp)
+        keep.append((k, kp))
+        counts.append(cnt)
+    pos, total = _positions(list(zip(items, counts)))
+    total = max([total] + [int(p.max()) + 1 for p in pos if p.size])
+    for g, p in enumerate(pos):
+        arr[g].positions = p.ctypes.data_as(C.POINTER(C.c_uint64))
+    fn = lib().afx_group_show_wire_rng if hasattr(ctx, "member") else lib().afx_show_wire_rng
+    rng = _device_rng(seed, stream)
+    out_len = C.c_size_t(0)
+    check(fn(ctx.h, arr, len(items), C.byref(rng), None, 0, C.byref(out_len), None, 0))
+    out = np.zeros(max(1, out_len.value), np.uint8)
+    status = np.full(max(1, total), 255, np.uint8)
+    check(fn(ctx.h, arr, len(items), C.byref(rng), out.ctypes.data, out.size, C.byref(out_len), status.ctypes.data, total))
+    shapes = [Shape.from_buffer_copy(bytes(arr[g].shape_out)) for g in range(len(items))]
+    return out[:out_len.value].tobytes(), shapes, status[:total]
+
+
 # ---- CredentialRequest batches ("AFXR" v1) and Issuer::issue over them --------------------------------
 def pack_requests(kinds, values):
     """kinds: AFX_ATTR_* per position; values [n,count,32] -> one AFXR section"""
@@ -222,4 +274,19 @@ def issue_wire(ctx, blob, rnd):
     out = np.zeros(max(1, out_len.value), np.uint8)
     status = np.full(max(1, cnt.value), 255, np.uint8)
     check(fn(ctx.h, blob, len(blob), C.byref(r), out.ctypes.data, out.size, C.byref(out_len), status.ctypes.data, status.size, C.byref(cnt)))
+    return out[:out_len.value].tobytes(), status[:cnt.value]
+
+
+def issue_wire_rng(ctx, blob, seed=None, stream=0):
+    """afx_issue_wire_rng (afx_group_issue_wire_rng for a Group): issue_wire with t_wide, U_wide and rng_seed drawn on the device from
+    (seed, stream) at each request's index in the stream -> (AFXI response bytes, status per request in stream order)"""
+    import ctypes as C
+    from . import check, lib
+    fn = lib().afx_group_issue_wire_rng if hasattr(ctx, "member") else lib().afx_issue_wire_rng
+    rng = _device_rng(seed, stream)
+    out_len, cnt = C.c_size_t(0), C.c_size_t(0)
+    check(fn(ctx.h, blob, len(blob), C.byref(rng), None, 0, C.byref(out_len), None, 0, C.byref(cnt)))
+    out = np.zeros(max(1, out_len.value), np.uint8)
+    status = np.full(max(1, cnt.value), 255, np.uint8)
+    check(fn(ctx.h, blob, len(blob), C.byref(rng), out.ctypes.data, out.size, C.byref(out_len), status.ctypes.data, status.size, C.byref(cnt)))
     return out[:out_len.value].tobytes(), status[:cnt.value]

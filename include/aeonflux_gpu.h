@@ -664,6 +664,59 @@ int afx_show_wire(afx_ctx* ctx, afx_show_group* groups, size_t n_groups, uint8_t
 int afx_group_show_wire(afx_group* group, afx_show_group* groups, size_t n_groups, uint8_t* out, size_t out_cap, size_t* out_len,
                         uint8_t* status, size_t status_len);
 
+/* ---- Randomness drawn on the device ----------------------------------------------------------
+ * The wire doors above take the random draws of every item from the host (afx_issue_randomness: 160 B per request,
+ * afx_show_randomness: 96 B + 32 B per hidden point per credential).  The *_rng forms draw them on the GPU instead, as a documented
+ * deterministic function of a 32-byte seed and a 64-bit stream number (normative):
+ *
+ *   draw(seed, stream, index, label) = SHAKE256("aeonflux-amd/device-rng/v1"     26 ASCII bytes, no terminator
+ *                                               || seed                          32 bytes
+ *                                               || u64le(stream) || u64le(index) 8 + 8 bytes
+ *                                               || u8(label))                    75 bytes: one block at SHAKE256's rate of 136
+ *                                      truncated to the label's length (AFX_DRAW_BYTES).
+ *
+ *  - An issuance draws labels AFX_DRAW_T_WIDE, AFX_DRAW_U_WIDE and AFX_DRAW_ISSUE_SEED: its t_wide, U_wide and rng_seed.  Its index
+ *    is the item's ordinal in the request stream (= its status index).
+ *  - A show draws AFX_DRAW_Z_WIDE (z_wide), AFX_DRAW_SHOW_SEED (rng_seed) and AFX_DRAW_ENC_SEED(j) (enc_seeds[j], the j-th SECRET_POINT
+ *    in position order).  Its index is the item's ordinal over the groups in group order: the counts of the earlier groups plus i,
+ *    whatever `positions` says.
+ * The calls are specified as equivalences, which is also how they are tested: afx_issue_wire_rng(ctx, blob, {S, k}, ...) returns the
+ * bytes, statuses, lengths and error codes afx_issue_wire(ctx, blob, rnd, ...) returns when rnd holds draw(S, k, i, .) for item i;
+ * afx_show_wire_rng likewise against afx_show_wire with every group's rnd filled at its ordinal indices.  The group forms give the
+ * one-context bytes however the items are split: a draw depends on the global index only.
+ *  - rng == NULL: AFX_E_BAD_ARGS.  out == NULL: the size query, nothing drawn.
+ *  - The seed is a secret: whoever holds it can recompute every nonce.  The library zeroes its copies (the pinned staging image and
+ *    the device staging area) when the call completes, failures included.  Never reuse a (seed, stream) pair: a caller that keeps one
+ *    seed gives every call its own stream.
+ * The Rust crate's own calls keep passing the crate's csprng draws (integration/: crate semantics); these forms are for C and Python
+ * servers on the wire doors. */
+#define AFX_DRAW_T_WIDE 0u
+#define AFX_DRAW_U_WIDE 1u
+#define AFX_DRAW_ISSUE_SEED 2u
+#define AFX_DRAW_Z_WIDE 3u
+#define AFX_DRAW_SHOW_SEED 4u
+#define AFX_DRAW_ENC_SEED(j) (5u + (uint32_t)(j))   /* j < AFX_MAX_ATTRIBUTES */
+#define AFX_DRAW_BYTES(label) (((label) == AFX_DRAW_T_WIDE || (label) == AFX_DRAW_U_WIDE || (label) == AFX_DRAW_Z_WIDE) ? 64u : 32u)
+/* (declared apart from its typedef: unlike the batch structs above, the Rust shim does not bind it - it keeps the crate's explicit draws,
+ * INTEGRATION.md - and tests/test_integration_layouts.py checks the typedef'd structs against the shim's) */
+struct afx_device_rng {
+  const uint8_t* seed;  /* 32 bytes, or NULL: the library reads 32 bytes from getrandom(2) for this call (one seed per group call) */
+  uint64_t stream;      /* a caller that keeps one seed gives every call its own stream; never reuse (seed, stream) */
+};
+typedef struct afx_device_rng afx_device_rng;
+/* out[i] = draw(seed, stream, first + i, label) for i < count: [count][AFX_DRAW_BYTES(label)] bytes (label <= AFX_DRAW_ENC_SEED(31)).
+ * `first` is the 64-bit index of the first draw (size_t: 64 bits on the LP64 hosts the library builds for). */
+int afx_rng_expand(afx_ctx* ctx, const afx_device_rng* rng, uint32_t label, size_t first, size_t count, uint8_t* out);
+int afx_issue_wire_rng(afx_ctx* ctx, const uint8_t* blob, size_t len, const afx_device_rng* rng, uint8_t* out, size_t out_cap,
+                       size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out);
+int afx_group_issue_wire_rng(afx_group* group, const uint8_t* blob, size_t len, const afx_device_rng* rng, uint8_t* out,
+                             size_t out_cap, size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out);
+/* groups[g].rnd is not read */
+int afx_show_wire_rng(afx_ctx* ctx, afx_show_group* groups, size_t n_groups, const afx_device_rng* rng, uint8_t* out, size_t out_cap,
+                      size_t* out_len, uint8_t* status, size_t status_len);
+int afx_group_show_wire_rng(afx_group* group, afx_show_group* groups, size_t n_groups, const afx_device_rng* rng, uint8_t* out,
+                            size_t out_cap, size_t* out_len, uint8_t* status, size_t status_len);
+
 /* ---- setup helpers (cold path; still GPU arithmetic) ---------------------------------------- */
 
 /* IssuerParameters::generate (src/parameters.rs:349-362) and W = w*G_w (src/amacs.rs:104): given
