@@ -108,6 +108,13 @@ class DeviceRng(C.Structure):
 
 
 DRAW_T_WIDE, DRAW_U_WIDE, DRAW_ISSUE_SEED, DRAW_Z_WIDE, DRAW_SHOW_SEED = 0, 1, 2, 3, 4
+DRAW_BATCH_WEIGHTS = 64   # the weights of a batchable verification: 16 bytes per commitment (not served by afx_rng_expand)
+
+
+class CommitmentsSoA(C.Structure):
+    """afx_commitments_soa: the commitments R_j of a batch of batchable presentations - main [n_main][count][32], one [5][count][32] array
+    per proof of encryption"""
+    _fields_ = [("main", C.c_void_p), ("enc", C.POINTER(C.c_void_p))]
 
 
 def DRAW_ENC_SEED(j):
@@ -260,6 +267,28 @@ def lib():
             for name in ("afx_show_wire_rng", "afx_group_show_wire_rng"):
                 getattr(_LIB, name).argtypes = [C.c_void_p, C.POINTER(ShowGroup), C.c_size_t, C.POINTER(DeviceRng), C.c_void_p, C.c_size_t,
                                                 C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t]
+        # (batchable presentation proofs: commitments instead of challenges, one weighted sum per item)
+        if hasattr(_LIB, "afx_verify_presentations_batchable"):
+            _LIB.afx_batchable_main_commitments.restype = C.c_uint32
+            _LIB.afx_batchable_main_commitments.argtypes = [C.c_void_p, C.POINTER(Shape)]
+            for name in ("afx_verify_presentations_batchable", "afx_verify_presentations_batchable_dev"):
+                getattr(_LIB, name).argtypes = [C.c_void_p, C.POINTER(Shape), C.POINTER(PresentationSoA), C.POINTER(CommitmentsSoA), C.POINTER(DeviceRng),
+                                                C.c_size_t, C.c_void_p]
+            for name in ("afx_show_batchable", "afx_show_batchable_dev"):
+                getattr(_LIB, name).argtypes = [C.c_void_p, C.POINTER(CredentialsSoA), C.POINTER(KeypairsSoA), C.POINTER(ShowRandomness), C.c_size_t,
+                                                C.POINTER(PresentationOut), C.POINTER(CommitmentsSoA), C.POINTER(Shape), C.c_void_p]
+        # (batchable presentations on bytes: wire_batchable.cpp, left out of the host-simulation builds of the engine's eight sources)
+        if hasattr(_LIB, "afx_show_batchable_wire"):
+            _LIB.afx_batchable_wire_header_bytes.restype = C.c_size_t
+            _LIB.afx_batchable_wire_header_bytes.argtypes = [C.POINTER(Shape)]
+            _LIB.afx_batchable_wire_cells_per_record.restype = C.c_uint32
+            _LIB.afx_batchable_wire_cells_per_record.argtypes = [C.POINTER(Shape), C.c_uint32]
+            _LIB.afx_batchable_wire_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(Shape), C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+            _LIB.afx_batchable_wire_section_bytes.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+            _LIB.afx_batchable_wire_pack.argtypes = [C.POINTER(Shape), C.POINTER(PresentationSoA), C.POINTER(CommitmentsSoA), C.c_uint32, C.c_size_t, C.c_void_p,
+                                                     C.c_size_t, C.POINTER(C.c_size_t)]
+            _LIB.afx_verify_presentations_batchable_wire.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(DeviceRng), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+            _LIB.afx_show_batchable_wire.argtypes = [C.c_void_p, C.POINTER(ShowGroup), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t]
         if hasattr(_LIB, "afx_issuer_keygen"):
             _LIB.afx_issuer_keygen.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p]
     return _LIB

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import (AttributesSoA, CredentialsSoA, EncProofOut, EncProofSoA, IssuanceGroup, IssuanceSoA, IssueGroup, IssueRandomness, KeypairsSoA,
+from . import (AttributesSoA, CommitmentsSoA, CredentialsSoA, DeviceRng, EncProofOut, EncProofSoA, IssuanceGroup, IssuanceSoA, IssueGroup, IssueRandomness, KeypairsSoA,
                PresentationOut, PresentationSoA, Shape, ShowGroup, ShowRandomness, check, lib)
 
 ENC_FIELDS = ("challenge", "responses", "pk", "E1", "E2", "C_y_1", "C_y_2", "C_y_3", "C_y_2p")
@@ -248,6 +248,66 @@ def verify_presentations(ctx, shape, p, first=None, n=None):
         check(lib().afx_group_verify_presentations(ctx.h, C.byref(shape), C.byref(soa), cnt, status.ctypes.data))
     else:
         check(lib().afx_verify_presentations(ctx.h, C.byref(shape), C.byref(soa), cnt, status.ctypes.data))
+    return status
+
+
+def commitments_soa(cm, ptr=lambda a: a.ctypes.data):
+    """afx_commitments_soa over dict(main [n_main,count,32], enc [[5,count,32] per proof of encryption]); returns (soa, keepalive)"""
+    encs = (C.c_void_p * max(1, len(cm["enc"])))(*[ptr(a) for a in cm["enc"]])
+    return CommitmentsSoA(ptr(cm["main"]), C.cast(encs, C.POINTER(C.c_void_p))), encs
+
+
+def device_rng(seed, stream=0):
+    """afx_device_rng; seed None: the library reads one from getrandom for the call"""
+    return DeviceRng(bytes(seed) if seed is not None else None, stream)
+
+
+def shape_of_kinds(kinds):
+    """the afx_shape afx_show derives from credential kinds (AFX_ATTR_*)"""
+    sh = Shape()
+    sh.n_attributes = len(kinds)
+    hs = ne = 0
+    for i, k in enumerate(kinds):
+        sh.kinds[i] = {0: 0, 1: 1, 4: 3}.get(k, 2)   # AFX_ENC_PUBLIC_SCALAR, _SECRET_SCALAR, _SECRET_POINT, else _PUBLIC_POINT
+        if k == 1:
+            sh.hidden_scalar_indices[hs] = i
+            hs += 1
+        elif k == 4:
+            sh.enc_indices[ne] = i
+            ne += 1
+    sh.n_hidden_scalars, sh.n_responses, sh.n_enc_proofs = hs, 3 + hs, ne
+    return sh
+
+
+def show_batchable(ctx, kinds, values, t, U, V, keypairs, z_wide, rng_seed, enc_seeds=None, M2=None, m3=None):
+    """AnonymousCredential::show with both encodings of every proof (afx_show_batchable): what show() returns plus the commitments,
+    dict(main [n_main,count,32], enc [[5,count,32] per proof of encryption]).  Returns (presentation, commitments, Shape, status)."""
+    cs, kp, rnd, out, o, cnt, keep = _show_args(kinds, values, t, U, V, keypairs, z_wide, rng_seed, enc_seeds, M2, m3)
+    sh0 = shape_of_kinds(kinds)
+    n_main = lib().afx_batchable_main_commitments(ctx.h, C.byref(sh0))
+    cm = {"main": np.zeros((n_main, cnt, 32), np.uint8), "enc": [np.zeros((5, cnt, 32), np.uint8) for _ in range(sh0.n_enc_proofs)]}
+    csoa, keep2 = commitments_soa(cm)
+    shape = Shape()
+    status = np.full(cnt, 255, np.uint8)
+    check(lib().afx_show_batchable(ctx.h, C.byref(cs), C.byref(kp) if kp is not None else None, C.byref(rnd), cnt, C.byref(out), C.byref(csoa),
+                                   C.byref(shape), status.ctypes.data))
+    return o, cm, shape, status
+
+
+def verify_presentations_batchable(ctx, shape, p, commitments, seed=None, stream=0):
+    """Issuer::verify over batchable presentations (afx_verify_presentations_batchable): p as for verify_presentations (its challenge
+    fields are not read and may be missing), commitments = dict(main, enc) as show_batchable returns them.  seed: 32 bytes for a
+    reproducible run; None draws the weights from a seed the library reads from getrandom."""
+    cnt = _u8(p["responses"]).shape[1]
+    zero = np.zeros((cnt, 32), np.uint8)
+    q = {f: _u8(p[f]) if p.get(f) is not None else zero for f in PRES_FIELDS}
+    q["enc"] = [{f: _u8(d[f]) if d.get(f) is not None else zero for f in ENC_FIELDS} for d in p["enc"]]
+    soa, keep = presentation_soa(q)
+    cm = {"main": _u8(commitments["main"]), "enc": [_u8(a) for a in commitments["enc"]]}
+    csoa, keep2 = commitments_soa(cm)
+    rng = device_rng(seed, stream)
+    status = np.full(cnt, 255, np.uint8)
+    check(lib().afx_verify_presentations_batchable(ctx.h, C.byref(shape), C.byref(soa), C.byref(csoa), C.byref(rng), cnt, status.ctypes.data))
     return status
 
 

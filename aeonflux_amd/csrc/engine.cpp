@@ -9,6 +9,10 @@
 #include <system_error>
 #include <stdexcept>
 
+// (a weak reference, like afxk_draw in plans.cpp: the host simulation builds of the engine link the launchers they need from
+// tests/hostsim, and only the batchable simulation brings this one)
+hipError_t afxk_coef(hipStream_t s, const afx_coef_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
+
 namespace afx {
 namespace { size_t job_size(LaunchKind k); }   // bytes of one job of a launch kind (below, with the relocation)
 
@@ -220,6 +224,7 @@ void Assembler::add_walk_rows(Launch& l, uint32_t per_row) {
   memcpy(blob_.data() + l.rows_off, rows.data(), sizeof(afx_walk_row) * rows.size());
 }
 void Assembler::scalarop(const std::vector<afx_scalarop_job>& jobs) { flush_maps(); add_jobs(L_SCALAROP, jobs); }
+void Assembler::coef(const std::vector<afx_coef_job>& jobs) { flush_maps(); add_jobs(L_COEF, jobs); }
 void Assembler::hash(const std::vector<afx_hash_program>& progs) {
   flush_maps();
   flush_encodings();   // encodings still queued (Assembler::pointop, compress_also, a small pass's stages) are launched before their reader
@@ -1040,6 +1045,7 @@ size_t job_size(LaunchKind k) {
     case L_NEGENC: return sizeof(afx_negenc_job);
     case L_TABLE_AFFINE: return sizeof(afx_table_job);
     case L_POWERS: return sizeof(afx_powers_job);
+    case L_COEF: return sizeof(afx_coef_job);
     default: return 0;
   }
 }
@@ -1103,6 +1109,7 @@ void Plan::relocate(uint8_t* nblob, uint8_t* nws, uint8_t* nin, uint8_t* nout) {
       case L_POWERS:
         for (uint32_t i = 0; i < l.njobs; i++) { afx_powers_job& j = ((afx_powers_job*)J)[i]; m.fix(j.src); for (uint32_t k = 0; k < AFX_POWERS_MAX; k++) m.fix(j.out[k]); }
         break;
+      case L_COEF: for (uint32_t i = 0; i < l.njobs; i++) { afx_coef_job& j = ((afx_coef_job*)J)[i]; m.fix(j.weights); m.fix(j.triples); m.fix(j.operands); m.fix(j.out); } break;
       case L_COPY: m.fix(l.in); m.fix(l.out); break;
       case L_KINDS: break;
     }
@@ -1314,6 +1321,10 @@ int run_plans(afx_ctx* ctx, int lane, Plan* const* plans, size_t n) {
       case L_TABLE_AFFINE: AFX_HIP(afxk_table_affine(s, (const afx_table_job*)jobs, (const afx_walk_row*)rows, nrows, passes, max_count)); break;
       case L_POINTSUM: AFX_HIP(afxk_pointsum(s, (const afx_pointsum_job*)jobs, nrows, rw, passes, max_count, odd, ctx->variants)); break;
       case L_POWERS: AFX_HIP(afxk_powers(s, (const afx_powers_job*)jobs, nrows, rw, passes, max_count)); break;
+      case L_COEF:
+        if (!afxk_coef) { set_error("batchable verification: no k_coef launcher in this build"); return AFX_E_NO_DEVICE; }
+        AFX_HIP(afxk_coef(s, (const afx_coef_job*)jobs, nrows, rw, passes, max_count));
+        break;
       case L_MSM_TABLES: AFX_HIP(afxk_msm_tables(s, odd, (const afx_table_job*)jobs, nrows, rw, passes, max_count)); break;
       case L_MSM_FIXED: case L_MSM_WINDOW: case L_MSM_NAF: {
         // pipelined lanes: the heavy kernel of one lane never runs beside the other lane's (only the light kernels
@@ -1529,10 +1540,107 @@ void SchnorrBuilder::verify_compact(const uint8_t* challenge_dev, uint32_t trace
   hash_out.push_back(p);
 }
 
+size_t BatchableSum::base_of(const int32_t* var, int32_t fixed) {
+  for (size_t i = 0; i < bases.size(); i++)
+    if (var ? bases[i].var == var : (!bases[i].var && bases[i].fixed == fixed)) return i;
+  Base b;
+  b.var = var; b.fixed = var ? -1 : fixed;
+  bases.push_back(b);
+  return bases.size() - 1;
+}
+uint16_t BatchableSum::operand_of(const uint8_t* dev) {
+  for (size_t i = 0; i < operands.size(); i++)
+    if (operands[i] == dev) return (uint16_t)i;
+  if (operands.size() >= AFX_COEF_ONE) throw std::length_error("too many operands in one weighted sum");
+  operands.push_back(dev);
+  return (uint16_t)(operands.size() - 1);
+}
+std::vector<int32_t*> BatchableSum::emit(Assembler& as, const uint8_t* weights, uint64_t stride, std::vector<afx_coef_job>& coef_out, std::vector<afx_msm_job>& msm_out) {
+  std::vector<int32_t*> parts;
+  if (bases.empty()) return parts;
+  const uint8_t* const* ops = as.put_ptrs(operands.data(), operands.size());
+  // per-item bases first, then the generators: every job is one doubling chain whatever it holds, so the terms are dealt out evenly
+  std::vector<size_t> order;
+  for (size_t i = 0; i < bases.size(); i++) if (bases[i].var) order.push_back(i);
+  for (size_t i = 0; i < bases.size(); i++) if (!bases[i].var) order.push_back(i);
+  const size_t n_jobs = (order.size() + AFX_MSM_MAX_TERMS - 1) / AFX_MSM_MAX_TERMS;
+  std::vector<std::vector<afx_msm_term>> terms(n_jobs);
+  for (size_t k = 0; k < order.size(); k++) {
+    const Base& b = bases[order[k]];
+    afx_coef_job cj;
+    memset(&cj, 0, sizeof cj);
+    cj.weights = weights; cj.stride = stride; cj.operands = ops;
+    cj.triples = as.put(b.triples.data(), b.triples.size());
+    cj.n_triples = (uint32_t)b.triples.size();
+    cj.out = as.new_enc();
+    coef_out.push_back(cj);
+    afx_msm_term t;
+    memset(&t, 0, sizeof t);
+    t.scalar = cj.out; t.scalar_stride = 32; t.fixed_idx = b.var ? -1 : b.fixed; t.var = b.var; t.negate = b.negate_term ? 1u : 0u;
+    terms[k * n_jobs / order.size()].push_back(t);
+  }
+  for (size_t i = 0; i < n_jobs; i++) {
+    afx_msm_job j;
+    memset(&j, 0, sizeof j);
+    order_terms(j, terms[i]);
+    j.out_var = as.new_var();
+    parts.push_back(j.out_var);
+    msm_out.push_back(j);
+  }
+  return parts;
+}
+
+bool SchnorrBuilder::verify_batchable(const uint8_t* const* commitments, size_t n_commitments, uint32_t trace_row, size_t total, size_t off, BatchableSum& sum,
+                                      std::vector<afx_decode_job>& decode_out, std::vector<afx_hash_program>& hash_out) {
+  if (n_commitments != constraints_.size()) return false;
+  afx_ctx* c = as_.ctx;
+  // the challenge: a scalar of the workspace, or the row of the challenge trace (which then is where the sum reads it)
+  uint8_t* chal = nullptr;
+  if (c->trace) {
+    if (total > c->trace_count || trace_row >= c->trace_rows) as_.plan_error = "challenge trace array too small for this call";
+    else chal = c->trace + ((size_t)trace_row * c->trace_count + off) * 32;
+  }
+  if (!chal) chal = as_.new_enc();
+  const uint16_t op_c = sum.operand_of(chal);
+  for (size_t j = 0; j < constraints_.size(); j++) {
+    const auto& cn = constraints_[j];
+    const uint16_t w = (uint16_t)(sum.n_weights + j);
+    auto add = [&](const PointVar& p, uint16_t operand, bool negate) {
+      if (!p.is_const && !p.var) throw std::logic_error("a term needs the coordinates of a point that was only encoded");
+      const bool neg = negate != (p.is_const ? p.neg : p.var_negated);
+      const afx_coef_triple t = { w, operand, (uint16_t)(neg ? 1 : 0), 0 };
+      sum.bases[sum.base_of(p.is_const ? nullptr : p.var, p.is_const ? (int32_t)p.gen : -1)].triples.push_back(t);
+    };
+    for (auto& sp : cn.second) add(points_[sp.second], sum.operand_of(scalars_[sp.first].dev), false);   // + rho_j * resp_s * P
+    add(points_[cn.first], op_c, true);                                                                  // - rho_j * c * LHS_j
+    // - rho_j * R_j: the received commitment, decoded; the weight itself is the coefficient and the term is subtracted
+    int32_t* v_R = as_.new_var();
+    const afx_decode_job dj = { commitments[j], v_R, 1, 0 };
+    decode_out.push_back(dj);
+    BatchableSum::Base& rb = sum.bases[sum.base_of(v_R, -1)];
+    rb.negate_term = true;
+    const afx_coef_triple tr = { w, (uint16_t)AFX_COEF_ONE, 0, 0 };
+    rb.triples.push_back(tr);
+    sim_.append_message_const("blindcom", (const uint8_t*)point_labels_[cn.first].c_str(), point_labels_[cn.first].size());
+    sim_.append_message_hole32("val", field_of(commitments[j]));
+  }
+  if (sum.n_weights + constraints_.size() >= AFX_COEF_ONE) throw std::length_error("too many constraints in one weighted sum");
+  sum.n_weights += (uint32_t)constraints_.size();
+  sim_.challenge64("chal", AFX_SQ_SCALAR_OUT, 0);
+  for (const uint8_t* f : fields_)
+    if (f == chal) throw std::logic_error("a transcript reads its own challenge");
+  afx_hash_program p = make_program(sim_);
+  uint8_t* couts[1] = { chal };
+  p.outs = as_.put_ptrs(couts, 1);
+  p.n_outs = 1;
+  hash_out.push_back(p);
+  return true;
+}
+
 void SchnorrBuilder::prove_compact(const uint8_t* rng_seed_dev, uint8_t* challenge_out, uint8_t* responses_out, size_t response_row_stride,
                                    std::vector<afx_hash_program>& rng_hash, std::vector<afx_msm_job>& msm_out,
                                    std::vector<afx_hash_program>& chal_hash, std::vector<afx_scalarop_job>& resp_ops,
-                                   std::vector<afx_scalarop_job>* pre_ops) {
+                                   std::vector<afx_scalarop_job>* pre_ops, uint8_t* const* commitments_out) {
   const size_t ns = scalars_.size();
   // TranscriptRngBuilder: clone, rekey with every witness, finalize with the external 32 bytes
   StrobeSim rng = sim_;
@@ -1562,6 +1670,7 @@ void SchnorrBuilder::prove_compact(const uint8_t* rng_seed_dev, uint8_t* challen
   }
   // the rng's last prf closes on a completed record, so emit() sees everything
   // commitments R_j = sum blind[s] * P
+  const size_t first_commitment = msm_out.size();
   for (auto& cn : constraints_) {
     std::vector<afx_msm_term> terms;
     for (auto& sp : cn.second) {
@@ -1594,7 +1703,7 @@ void SchnorrBuilder::prove_compact(const uint8_t* rng_seed_dev, uint8_t* challen
     afx_msm_job j;
     memset(&j, 0, sizeof j);
     order_terms(j, terms);
-    j.out_enc = as_.new_enc();
+    j.out_enc = commitments_out ? commitments_out[msm_out.size() - first_commitment] : as_.new_enc();
     msm_out.push_back(j);
     sim_.append_message_const("blindcom", (const uint8_t*)point_labels_[cn.first].c_str(), point_labels_[cn.first].size());
     sim_.append_message_hole32("val", field_of(j.out_enc));

@@ -196,6 +196,9 @@ struct afx_ctx {
     size_t pin_in_cap = 0;           // here on the host and go to HBM in one copy (statements.hpp Stager::upload); wiped on destroy
     hipEvent_t pin_in_done = nullptr;   // end of the copy that last read pin_in
     afx::DevBuf draw_jobs;           // the k_draw rows (and seed wipes) of the lane's latest device-drawn call (statements.hpp Stager::draw)
+    afx::DevBuf weights;             // batchable verification: 256 bytes for the staged seed, then the call's weights [n_weights][count][16]
+    void* weights_pin = nullptr;     // pinned image of the 40 seed bytes on their way to `weights` (zeroed once copied)
+    hipEvent_t weights_copied = nullptr;
   } lane[5];   // AFX_LANES: large calls alternate between lanes 0 and 1 (host_pipe, pipelining); the coalescer's sessions take whichever is free
   static constexpr int AFX_LANES = 5;
   bool pipelining = false;
@@ -264,7 +267,7 @@ namespace afx {
 
 // L_MSM_WINDOW keeps the slot the single k_msm kernel had (timing names: statements.cpp KIND_NAMES)
 enum LaunchKind { L_FILL_BAD, L_DECODE, L_SCCHECK, L_POINTOP, L_SCALAROP, L_MSM_WINDOW, L_HASH, L_FROM_UNIFORM, L_REDUCE_WIDE, L_COPY, L_FINISH,
-                  L_MSM_FIXED, L_MSM_NAF, L_MSM_TABLES, L_COMPRESS, L_POINTSUM, L_NEGENC, L_TABLE_AFFINE, L_POWERS, L_KINDS };
+                  L_MSM_FIXED, L_MSM_NAF, L_MSM_TABLES, L_COMPRESS, L_POINTSUM, L_NEGENC, L_TABLE_AFFINE, L_POWERS, L_COEF, L_KINDS };
 // the kernels whose grid rows WALK a range of the launch's jobs (afx_walk_row) instead of taking one job each (afx_row)
 inline bool walks(LaunchKind k) { return k == L_COMPRESS || k == L_NEGENC || k == L_TABLE_AFFINE; }
 
@@ -346,6 +349,7 @@ class Assembler {
   void pointop(const std::vector<afx_pointop_job>& jobs);
   void negenc(const std::vector<afx_negenc_job>& jobs);   // encodings of the negations of decoded points, one inversion per item
   void scalarop(const std::vector<afx_scalarop_job>& jobs);
+  void coef(const std::vector<afx_coef_job>& jobs);   // the coefficients of a batchable verification's weighted sum (plan.h afx_coef_job)
   void msm(std::vector<afx_msm_job> jobs);   // assigns digit/table slots; small batches: one chain per term (msm_split)
   // one more point for the NEXT msm() call's k_compress2x launch: out_enc = encoding of +-2 * var, where var is (or will be, by
   // that call's chains) the half some job left (afx_msm_job.leave_half) - the "-E1" of a proof of encryption being created
@@ -455,6 +459,29 @@ struct ScalarVar {
   Enc host{};   // only for stride == 0 (needed as constant bytes in the prover's rng rekeying)
 };
 
+// The ONE weighted sum that checks every constraint of the proofs of a presentation in their batchable form (zkp's BatchableProof:
+// the prover sends its commitments R_j instead of the challenge; include/aeonflux_gpu.h):
+//     sum_j rho_j * ( sum_s resp_s * P_(j,s) - c * LHS_j - R_j ) == identity,  rho_j a 128-bit weight per (item, proof, constraint).
+// Every SchnorrBuilder::verify_batchable of the presentation adds its constraints here: terms on the same base merge into one
+// coefficient (afx_coef_job), whichever constraint or proof they come from.  emit() then lays out the k_coef launch and the
+// multiscalar jobs of the sum (as many as AFX_MSM_MAX_TERMS demands) and returns the variables that hold their results.
+struct BatchableSum {
+  struct Base {
+    const int32_t* var = nullptr;   // per-item point, or
+    int32_t fixed = -1;             // generator id
+    bool negate_term = false;       // the coefficient is kept positive and the TERM subtracted (received commitments: the coefficient
+                                    // is the 128-bit weight itself, not its 252-bit negation)
+    std::vector<afx_coef_triple> triples;
+  };
+  std::vector<Base> bases;
+  std::vector<const uint8_t*> operands;   // response and challenge arrays, [count][32]
+  uint32_t n_weights = 0;
+  size_t base_of(const int32_t* var, int32_t fixed);
+  uint16_t operand_of(const uint8_t* dev);
+  // weights: [n_weights][stride][16] on the device, pointing at this pass's first item
+  std::vector<int32_t*> emit(Assembler& as, const uint8_t* weights, uint64_t stride, std::vector<afx_coef_job>& coef_out, std::vector<afx_msm_job>& msm_out);
+};
+
 // zkp::toolbox::{prover::Prover, verifier::Verifier} + SchnorrCS, batch form.
 class SchnorrBuilder {
  public:
@@ -469,12 +496,20 @@ class SchnorrBuilder {
   // c * coef_k go here (run them before msm_out, after whatever computes the coefficients)
   void verify_compact(const uint8_t* challenge_dev, uint32_t trace_row, size_t total, size_t off, std::vector<afx_msm_job>& msm_out, std::vector<afx_hash_program>& hash_out,
                       std::vector<afx_scalarop_job>* pre_ops = nullptr, std::vector<afx_scalarop_job>* expand_ops = nullptr);
+  // Verifier::verify_batchable over the batch: `commitments[j]` is the [count][32] array of the received R_j (constraint order).  They
+  // become transcript fields and decode jobs (the identity encoding fails the item, zkp's validate_and_append_blinding_commitment);
+  // the challenge is squeezed as a scalar (into the challenge trace's row when one is set) and the constraints join `sum`.
+  // Returns false when `n_commitments` is not the number of constraints (the caller's shape bookkeeping is wrong).
+  bool verify_batchable(const uint8_t* const* commitments, size_t n_commitments, uint32_t trace_row, size_t total, size_t off, BatchableSum& sum,
+                        std::vector<afx_decode_job>& decode_out, std::vector<afx_hash_program>& hash_out);
+  size_t num_constraints() const { return constraints_.size(); }
   // Prover::prove_compact over the batch.  Fills: rng hash program (blindings), commitment msm jobs,
   // challenge hash program, response scalar ops.  rng_seed_dev: [count][32].
   void prove_compact(const uint8_t* rng_seed_dev, uint8_t* challenge_out, uint8_t* responses_out /* [nsc][count][32] */,
                      size_t response_row_stride, std::vector<afx_hash_program>& rng_hash, std::vector<afx_msm_job>& msm_out,
                      std::vector<afx_hash_program>& chal_hash, std::vector<afx_scalarop_job>& resp_ops,
-                     std::vector<afx_scalarop_job>* pre_ops = nullptr);
+                     std::vector<afx_scalarop_job>* pre_ops = nullptr, uint8_t* const* commitments_out = nullptr);
+  // (commitments_out: the batchable form - the [count][32] array that receives the encoding of commitment j, which the compact form drops)
   size_t num_scalars() const { return scalars_.size(); }
 
  private:

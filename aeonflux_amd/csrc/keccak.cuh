@@ -91,9 +91,9 @@ __device__ __forceinline__ void keccak_f1600(uint64_t st[25]) {
 // first lanes of the state (64 bytes at most, within the rate).  `ss`: the 40 staged bytes seed || u64le(stream) as five
 // little-endian words.  The 26-byte prefix leaves the message 2 bytes off the lane grid: lane L >= 4 holds word L - 4 of
 // seed || stream || index || label shifted by 16 bits.
-__device__ __forceinline__ void shake256_draw(uint64_t out[8], const uint64_t ss[5], uint64_t index, uint32_t label) {
+// the padded block of a draw's message as a sponge state, not yet permuted
+__device__ __forceinline__ void shake256_draw_block(uint64_t st[25], const uint64_t ss[5], uint64_t index, uint32_t label) {
   const uint64_t w[7] = { ss[0], ss[1], ss[2], ss[3], ss[4], index, (uint64_t)(label & 0xffu) };
-  uint64_t st[25];
   st[0] = 0x78756c666e6f6561ULL;   // "aeonflux"
   st[1] = 0x7665642f646d612dULL;   // "-amd/dev"
   st[2] = 0x2f676e722d656369ULL;   // "ice-rng/"
@@ -104,7 +104,26 @@ __device__ __forceinline__ void shake256_draw(uint64_t out[8], const uint64_t ss
 #pragma unroll
   for (int l = 10; l < 25; l++) st[l] = 0;
   st[16] = 0x80ULL << 56;          // byte 135: the last padding bit of the block
+}
+__device__ __forceinline__ void shake256_draw(uint64_t out[8], const uint64_t ss[5], uint64_t index, uint32_t label) {
+  uint64_t st[25];
+  shake256_draw_block(st, ss, index, label);
   keccak_f1600(st);
 #pragma unroll
   for (int l = 0; l < 8; l++) out[l] = st[l];
+}
+// A draw longer than the 64 bytes above (the weights of a batchable verification: 16 bytes per commitment): the first n_words
+// 64-bit words of the same SHAKE256 output, squeezed over as many blocks of the 136-byte rate (17 words) as that takes and handed
+// to store(k, word) in order.  The state stays in registers: the block loop is not unrolled, the 17 words of a block are.
+template <class Store>
+__device__ __forceinline__ void shake256_draw_words(const uint64_t ss[5], uint64_t index, uint32_t label, uint32_t n_words, Store store) {
+  uint64_t st[25];
+  shake256_draw_block(st, ss, index, label);
+#pragma unroll 1
+  for (uint32_t w0 = 0; w0 < n_words; w0 += 17) {
+    keccak_f1600(st);
+#pragma unroll
+    for (int l = 0; l < 17; l++)
+      if (w0 + l < n_words) store(w0 + l, st[l]);
+  }
 }

@@ -54,3 +54,8 @@ hipError_t afxk_aos_to_soa(hipStream_t s, const uint8_t* rec, uint8_t* soa, cons
 hipError_t afxk_soa_to_aos(hipStream_t s, const uint8_t* soa, uint8_t* rec, const uint32_t* row_of_cell, const uint8_t* status_dev, uint32_t cells, uint32_t count);
 // device draws: grid row r fills jobs[r] (a device array; plan.h afx_draw_job); `max_count` = the largest count among them
 hipError_t afxk_draw(hipStream_t s, const afx_draw_job* jobs, uint32_t njobs, uint32_t max_count);
+// batchable presentation proofs (batchable.cuh, the last part of kernels.hip): weights[w][item] (16 bytes each, w < n_weights) = the first 16 * n_weights bytes of
+// draw(seed, stream, index0 + item, label); `seed` = the 40 staged bytes seed || u64le(stream) on the device
+hipError_t afxk_batch_weights(hipStream_t s, const uint8_t* seed, uint64_t index0, uint32_t label, uint32_t n_weights, uint32_t count, uint8_t* weights);
+// one coefficient of the weighted sum per job (plan.h afx_coef_job)
+hipError_t afxk_coef(hipStream_t s, const afx_coef_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count);

@@ -2035,3 +2035,6 @@ hipError_t afxk_draw(hipStream_t s, const afx_draw_job* jobs, uint32_t njobs, ui
   hipLaunchKernelGGL(k_draw, dim3((max_count + AFX_BLOCK - 1) / AFX_BLOCK, njobs), dim3(AFX_BLOCK), 0, s, jobs, (const afx_row*)nullptr);
   return hipGetLastError();
 }
+
+// the coefficient stage of the batchable presentation proofs: its two kernels and their launchers
+#include "batchable.cuh"

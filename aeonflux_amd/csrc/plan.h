@@ -119,6 +119,25 @@ typedef struct { const uint8_t* seed; uint8_t* dst; uint64_t index; uint32_t cou
 /* bytes of one draw: t_wide, U_wide and z_wide are 64 (include/aeonflux_gpu.h AFX_DRAW_*), the seeds 32 */
 #define AFX_DRAW_LEN(label) (((label) == 0u || (label) == 1u || (label) == 3u) ? 64u : 32u)
 
+/* k_coef (batchable presentation proofs, include/aeonflux_gpu.h): the scalars of the ONE weighted sum that checks every constraint
+ * of a presentation's proofs.  One job = one output scalar array (the coefficient of one base of the sum), one grid row per job, one
+ * lane per item:  out[i] = sum over the job's triples of  +-weight[t.weight][i] * operand[t.operand][i]  mod l, where a weight is the
+ * 128-bit factor of one (proof, constraint) and an operand a response or challenge array (operand AFX_COEF_ONE: the constant 1 - the
+ * coefficient of a received commitment is its weight itself).  The triples are wave-uniform: scalar loads, uniform branches. */
+#define AFX_COEF_ONE 0xffffu
+typedef struct { uint16_t weight, operand, negate, pad; } afx_coef_triple;
+typedef struct {
+  const uint8_t* weights;          /* [n_weights][stride][16], little-endian 128-bit values (k_batch_weights); points at the pass's
+                                      first item of weight 0                                                                   */
+  const afx_coef_triple* triples;
+  const uint8_t* const* operands;  /* device table of [count][32] scalar arrays (shared by the jobs of a pass)                  */
+  uint8_t* out;                    /* [count][32]                                                                              */
+  uint64_t stride;                 /* items of the whole call: the length of a weight row                                      */
+  uint32_t n_triples, pad;
+} afx_coef_job;
+/* bytes one item draws per weight under AFX_DRAW_BATCH_WEIGHTS */
+#define AFX_WEIGHT_BYTES 16u
+
 /* variable point storage: struct-of-arrays, limb (c*9+l) of item i at base[(c*9+l)*count + i] */
 typedef int32_t* afx_var_t;
 

@@ -39,7 +39,7 @@ extern "C" void* afx_ctx_stream(const afx_ctx* ctx) { return ctx ? (void*)ctx->s
 
 // indexed by afx::LaunchKind.  "k_msm" (afx_ctx_get_timing) = the three chain kernels + the table kernel together
 static const char* const KIND_NAMES[] = { "k_fill_u32", "k_decode", "k_sccheck", "k_pointop", "k_scalarop", "k_msm_window", "k_hash",
-                                          "k_from_uniform", "k_reduce_wide", "copy", "k_finish", "k_msm_fixed", "k_msm_naf", "k_msm_tables", "k_compress2x", "k_pointsum", "k_negenc", "k_table_affine", "k_powers" };
+                                          "k_from_uniform", "k_reduce_wide", "copy", "k_finish", "k_msm_fixed", "k_msm_naf", "k_msm_tables", "k_compress2x", "k_pointsum", "k_negenc", "k_table_affine", "k_powers", "k_coef" };
 static_assert(sizeof KIND_NAMES / sizeof KIND_NAMES[0] == afx::L_KINDS, "one name per launch kind");
 static int drain_timing(afx_ctx* c) {
   for (auto& L : c->lane)
@@ -263,6 +263,9 @@ extern "C" void afx_ctx_destroy(afx_ctx* c) {
     L.staging.release(true);
     L.staging_out.release(true);
     L.draw_jobs.release(true);
+    L.weights.release(true);
+    if (L.weights_pin) { memset(L.weights_pin, 0, 64); (void)hipHostFree(L.weights_pin); L.weights_pin = nullptr; }
+    if (L.weights_copied) { (void)hipEventDestroy(L.weights_copied); L.weights_copied = nullptr; }
     if (L.pin) { memset(L.pin, 0, L.pin_cap); (void)hipHostFree(L.pin); L.pin = nullptr; L.pin_cap = 0; }
     if (L.pin_in) { memset(L.pin_in, 0, L.pin_in_cap); (void)hipHostFree(L.pin_in); L.pin_in = nullptr; L.pin_in_cap = 0; }
     if (L.pin_in_done) { (void)hipEventDestroy(L.pin_in_done); L.pin_in_done = nullptr; }
@@ -406,11 +409,22 @@ extern "C" int afx_ctx_create(afx_ctx** out, int device, const uint8_t* sysparam
 } catch (...) { return afx::exception_rc(); }
 
 // ProofOfEncryption::verify, src/nizk/encryption.rs:154-210
-static void add_encproof_verify(Assembler& as, JobSets& js, uint16_t index, const afx_encproof_soa& e, size_t total, size_t off, uint32_t trace_row) {
+// The batchable form of a presentation being verified (include/aeonflux_gpu.h): where its received commitments lie, and the weighted
+// sum its proofs' constraints are collected into.
+struct BatchableIn {
+  const uint8_t* main = nullptr;          // [n_main][total][32]
+  const uint8_t* const* enc = nullptr;    // per proof of encryption: [5][total][32]
+  uint32_t n_main = 0;
+  const uint8_t* weights = nullptr;       // [n_weights][total][16] on the device (k_batch_weights)
+  BatchableSum sum;
+};
+// `commitments` (with `sum`): the batchable form - the proof's five received commitments, [5][total][32]
+static void add_encproof_verify(Assembler& as, JobSets& js, uint16_t index, const afx_encproof_soa& e, size_t total, size_t off, uint32_t trace_row,
+                                BatchableSum* sum = nullptr, const uint8_t* commitments = nullptr) {
   afx_ctx* c = as.ctx;
   auto row = [&](const uint8_t* base, size_t k) { return base + (k * total + off) * 32; };
   if (index >= c->n) { as.fail_all = true; return; }   // G_m[self.index] panics, encryption.rs:179
-  js.sccheck.push_back({ row(e.challenge, 0) });
+  if (!sum) js.sccheck.push_back({ row(e.challenge, 0) });
   for (int k = 0; k < 6; k++) js.sccheck.push_back({ row(e.responses, k) });
   int32_t *v_pk = as.new_var(), *v_E1 = as.new_var(), *v_E2 = as.new_var(), *v_Cy1 = as.new_var(), *v_Cy2 = as.new_var(),
           *v_Cy3 = as.new_var(), *v_Cy2p = as.new_var(), *v_D1 = as.new_var();
@@ -457,6 +471,12 @@ static void add_encproof_verify(Assembler& as, JobSets& js, uint16_t index, cons
   v.constrain(C_y_2p, { { a1, C_y_2 } });
   v.constrain(E1, { { a0, C_y_2 }, { m3, C_y_2p }, { z1, G_y_2 } });
   v.constrain(C_y_3, { { z, G_y_3 }, { m3, G_m_3 } });
+  if (sum) {
+    const uint8_t* R[5];
+    for (size_t j = 0; j < 5; j++) R[j] = row(commitments, j);
+    if (!v.verify_batchable(R, 5, trace_row, total, off, *sum, js.decode, js.hash)) throw std::logic_error("a proof of encryption has five constraints");
+    return;
+  }
   v.verify_compact(row(e.challenge, 0), trace_row, total, off, js.msm1, js.hash);
 }
 
@@ -508,8 +528,9 @@ static bool presentation_shape_rejects(const afx_ctx* c, const afx_shape& sh, ui
 }
 
 // Issuer::verify -> ProofOfValidCredential::verify, src/nizk/presentation.rs:324-443
+// `bi`: the batchable form (no challenges; commitments and weights instead)
 static void build_presentation_verify(Assembler& as, const afx_shape& sh, const afx_presentation_soa& b, size_t total, size_t off,
-                                      uint8_t* status_dev) {
+                                      uint8_t* status_dev, BatchableIn* bi = nullptr) {
   afx_ctx* c = as.ctx;
   JobSets js;
   auto row = [&](const uint8_t* base, size_t k) { return base + (k * total + off) * 32; };
@@ -519,7 +540,7 @@ static void build_presentation_verify(Assembler& as, const afx_shape& sh, const 
   if (presentation_shape_rejects(c, sh, keep, &k, hidden_slot, pos)) as.fail_all = true;
   if (as.fail_all) { emit(as, js, status_dev, AFX_ST_VERIFICATION_FAILURE); return; }
 
-  js.sccheck.push_back({ row(b.challenge, 0) });
+  if (!bi) js.sccheck.push_back({ row(b.challenge, 0) });
   for (uint32_t r = 0; r < sh.n_responses; r++) js.sccheck.push_back({ row(b.responses, r) });
   int32_t *v_Cx0 = as.new_var(), *v_Cx1 = as.new_var(), *v_CV = as.new_var(), *v_A = as.new_var(), *v_Z = as.new_var();
   uint8_t* e_Z = as.new_enc();
@@ -603,7 +624,7 @@ static void build_presentation_verify(Assembler& as, const afx_shape& sh, const 
   PointVar pZ = PointVar::Var(v_Z, e_Z);
   // (not with secret-independent addressing: the products c*x0 ... are the key times a public factor, and the expanded terms would
   // have to scan their tables like Z's own do - the second chain is the cheaper price there)
-  const bool expand_Z = as.small() && !c->secure_plan(false);
+  const bool expand_Z = !bi && as.small() && !c->secure_plan(false);
   if (expand_Z) {
     pZ.parts.push_back({ nullptr, 0, false, v_A, -1 });
     for (const afx_msm_term& t : zterms) pZ.parts.push_back({ t.scalar, t.scalar_stride, true, t.var, t.fixed_idx });
@@ -618,6 +639,43 @@ static void build_presentation_verify(Assembler& as, const afx_shape& sh, const 
     else v.constrain(C_y[j], { { z, G_y[p] } });
   }
   for (int d = 0; d < nD; d++) v.constrain(D[d], { { z, G_y[D_pos[d]] }, { z, neg_G_y_1 } });
+  if (bi) {
+    // Batchable form.  Z stays its own job, exactly as above (the issuer key's terms, under the context's secret mode and key schedule),
+    // and enters the sum as a per-item base; every scalar of the sum itself is public.  Order: Z and the other transcript points, the
+    // transcripts (challenges out), the coefficients, the sum over the main proof AND the proofs of encryption, its identity test.
+    std::vector<const uint8_t*> R(v.num_constraints());
+    for (size_t j = 0; j < R.size(); j++) R[j] = row(bi->main, j);
+    if (!v.verify_batchable(R.data(), bi->n_main, 0, total, off, bi->sum, js.decode, js.hash)) {
+      as.plan_error = "the shape's main proof does not have that many commitments";
+      as.finish(status_dev, AFX_ST_VERIFICATION_FAILURE);
+      return;
+    }
+    for (uint32_t e = 0; e < sh.n_enc_proofs; e++) add_encproof_verify(as, js, sh.enc_indices[e], b.enc[e], total, off, 1 + e, &bi->sum, bi->enc[e]);
+    as.sccheck(js.sccheck);
+    as.decode(js.decode);
+    as.scalarop(js.scalarop);
+    as.pointop(js.pointop);
+    as.negenc(js.negenc);
+    as.msm(js.msm1);
+    as.hash(js.hash);
+    std::vector<afx_coef_job> coefs;
+    std::vector<afx_msm_job> sums;
+    std::vector<int32_t*> parts = bi->sum.emit(as, bi->weights + off * AFX_WEIGHT_BYTES, total, coefs, sums);
+    as.coef(coefs);
+    as.msm(sums);
+    // the sum must BE the ristretto255 identity: tested on its encoding (32 zero bytes for all four points of the identity's coset)
+    const int32_t* acc = parts.at(0);
+    for (size_t k = 1; k + 1 < parts.size(); k++) {
+      int32_t* nv = as.new_var();
+      const afx_pointop_job add = { acc, parts[k], nullptr, +1, +1, nv, nullptr, 0 };
+      as.pointop({ add });
+      acc = nv;
+    }
+    const afx_pointop_job last = { acc, parts.size() > 1 ? parts.back() : nullptr, nullptr, +1, parts.size() > 1 ? +1 : 0, nullptr, as.new_enc(), 2u };
+    as.pointop({ last });
+    as.finish(status_dev, AFX_ST_VERIFICATION_FAILURE);
+    return;
+  }
   // one launch for everything: the lane that finishes Z goes straight on to constraint #1 (Z = z*I), the only job that needs it
   const size_t first_constraint = js.msm1.size();
   v.verify_compact(row(b.challenge, 0), 0, total, off, js.msm1, js.hash, nullptr, expand_Z ? &js.scalarop2 : nullptr);
@@ -662,6 +720,134 @@ extern "C" int afx_verify_presentations_dev(afx_ctx* ctx, const afx_shape* shape
     bb.enc = encs.data();
     build_presentation_verify(as, sh, bb, count, off, status_dev + off);
   }, key);
+} catch (...) { return afx::exception_rc(); }
+
+// ------------------------------------------------------------------------------------------------
+// batchable presentation proofs: the verifier (include/aeonflux_gpu.h)
+// ------------------------------------------------------------------------------------------------
+// (weak, like afxk_coef in engine.cpp: a host simulation that never verifies a batchable proof links without it)
+hipError_t afxk_batch_weights(hipStream_t s, const uint8_t* seed, uint64_t index0, uint32_t label, uint32_t n_weights, uint32_t count, uint8_t* weights) __attribute__((weak));
+
+extern "C" uint32_t afx_batchable_main_commitments(const afx_ctx* ctx, const afx_shape* shape) {
+  if (!ctx || !shape) return 0;
+  uint32_t keep[AFX_MAX_ATTRIBUTES], pos[AFX_MAX_ATTRIBUTES], k = 0;
+  int slot[AFX_MAX_ATTRIBUTES];
+  if (presentation_shape_rejects(ctx, *shape, keep, &k, slot, pos)) return 0;
+  return afx_batchable_n_main_of(*shape, ctx->strict);
+}
+
+// the call's weights on the lane its plans will run on: seed to the device, one k_batch_weights launch, seed zeroed (device and pinned image)
+static int draw_weights(afx_ctx* ctx, const afx_device_rng* rng, uint32_t n_weights, size_t count, const uint8_t** weights_out) {
+  if (!afxk_batch_weights) { set_error("batchable verification: no k_batch_weights launcher in this build"); return AFX_E_NO_DEVICE; }
+  if (count > 0xffffffffull) { set_error("too many items in one call"); return AFX_E_BAD_ARGS; }
+  AFX_HIP(hipSetDevice(ctx->device));
+  afx::Session* ses = (ctx->session && !ctx->session->paused) ? ctx->session : nullptr;
+  const int lane = ses ? ses->lane : (ctx->force_lane >= 0 ? ctx->force_lane : (ctx->pipelining ? (int)(ctx->lane_next & 1u) : 0));   // run_chunked's choice
+  afx_ctx::Lane& L = ctx->lane[lane];
+  int rc = L.weights.ensure(256 + (size_t)n_weights * count * AFX_WEIGHT_BYTES);
+  if (rc) return rc;
+  if (!L.weights_pin) AFX_HIP(hipHostMalloc(&L.weights_pin, 64, hipHostMallocDefault));
+  if (!L.weights_copied) AFX_HIP(hipEventCreateWithFlags(&L.weights_copied, hipEventDisableTiming));
+  afx_device_rng r = { nullptr, 0 };
+  if (rng) r = *rng;
+  DrawSeed seed;
+  if ((rc = seed.init(&r))) return rc;
+  memcpy(L.weights_pin, seed.b, 40);
+  uint8_t* d_seed = (uint8_t*)L.weights.p;
+  hipError_t e = hipMemcpyAsync(d_seed, L.weights_pin, 40, hipMemcpyHostToDevice, L.stream);
+  if (e == hipSuccess) e = hipEventRecord(L.weights_copied, L.stream);
+  if (e == hipSuccess) e = afxk_batch_weights(L.stream, d_seed, 0, AFX_DRAW_BATCH_WEIGHTS, n_weights, (uint32_t)count, d_seed + 256);
+  const hipError_t e2 = hipMemsetAsync(d_seed, 0, 40, L.stream);
+  (void)hipEventSynchronize(L.weights_copied);
+  afx_wipe(L.weights_pin, 64);
+  if (e != hipSuccess || e2 != hipSuccess) { set_error(std::string("batchable weights: ") + hipGetErrorString(e != hipSuccess ? e : e2)); return AFX_E_HIP; }
+  *weights_out = d_seed + 256;
+  return AFX_OK;
+}
+
+extern "C" int afx_verify_presentations_batchable_dev(afx_ctx* ctx, const afx_shape* shape, const afx_presentation_soa* batch, const afx_commitments_soa* commitments,
+                                                      const afx_device_rng* weights, size_t count, uint8_t* status_dev) try {
+  CtxLock lock__(ctx);
+  if (!ctx || !shape || !batch || !commitments || !status_dev) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  if (!ctx->has_key) { set_error("Issuer::verify needs the issuer key"); return AFX_E_NO_KEY; }
+  if (count == 0) return AFX_OK;
+  if (shape->n_enc_proofs && shape->n_enc_proofs <= AFX_MAX_ATTRIBUTES && !batch->enc) { set_error("enc proofs missing"); return AFX_E_BAD_ARGS; }
+  const afx_shape sh = *shape;
+  const afx_presentation_soa b = *batch;
+  const uint32_t n_main = afx_batchable_main_commitments(ctx, &sh);
+  std::vector<const uint8_t*> cenc;
+  if (n_main) {   // (0: a shape every item fails on, which reads no array)
+    bool missing = !b.C_x_0 || !b.C_x_1 || !b.C_V || (sh.n_attributes && !b.C_y) || (sh.n_responses && !b.responses) || !commitments->main ||
+                   (sh.n_enc_proofs && !commitments->enc);
+    for (uint32_t i = 0; i < sh.n_attributes; i++)
+      if ((sh.kinds[i] == AFX_ENC_PUBLIC_SCALAR || sh.kinds[i] == AFX_ENC_PUBLIC_POINT) && !b.attr_values) missing = true;
+    for (uint32_t e = 0; e < sh.n_enc_proofs && !missing; e++) {
+      const afx_encproof_soa& q = b.enc[e];
+      missing |= !q.responses || !q.pk || !q.E1 || !q.E2 || !q.C_y_1 || !q.C_y_2 || !q.C_y_3 || !q.C_y_2p || !commitments->enc[e];
+    }
+    if (missing) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
+    for (uint32_t e = 0; e < sh.n_enc_proofs; e++) cenc.push_back(commitments->enc[e]);
+  }
+  std::vector<afx_encproof_soa> encs;
+  if (b.enc && sh.n_enc_proofs <= AFX_MAX_ATTRIBUTES) encs.assign(b.enc, b.enc + sh.n_enc_proofs);
+  const uint8_t* d_weights = nullptr;
+  if (n_main) {
+    const int rc = draw_weights(ctx, weights, n_main + 5 * sh.n_enc_proofs, count, &d_weights);
+    if (rc) return rc;
+  }
+  return run_chunked(ctx, count, [&](Assembler& as, size_t off, uint32_t) {
+    afx_presentation_soa bb = b;
+    bb.enc = encs.data();
+    BatchableIn bi;
+    bi.main = commitments->main; bi.enc = cenc.data(); bi.n_main = n_main; bi.weights = d_weights;
+    build_presentation_verify(as, sh, bb, count, off, status_dev + off, &bi);
+  });
+} catch (...) { return afx::exception_rc(); }
+
+extern "C" int afx_verify_presentations_batchable(afx_ctx* ctx, const afx_shape* shape, const afx_presentation_soa* b, const afx_commitments_soa* cm,
+                                                  const afx_device_rng* weights, size_t count, uint8_t* status) try {
+  CtxLock lock__(ctx);   // (a batchable call takes the context in turn: it joins no collecting session)
+  if (!ctx || !shape || !b || !cm || !status) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  if (count == 0) return AFX_OK;
+  AFX_HIP(hipSetDevice(ctx->device));
+  if (!ctx->has_key) { set_error("Issuer::verify needs the issuer key"); return AFX_E_NO_KEY; }
+  const uint32_t n_main = afx_batchable_main_commitments(ctx, shape);
+  if (!n_main) { memset(status, AFX_ST_VERIFICATION_FAILURE, count); return AFX_OK; }   // a shape every item fails on: no array is read
+  const uint32_t na = shape->n_attributes, nr = shape->n_responses, ne = shape->n_enc_proofs;
+  bool missing = !b->C_x_0 || !b->C_x_1 || !b->C_V || (na && !b->C_y) || (nr && !b->responses) || (ne && (!b->enc || !cm->enc)) || !cm->main;
+  for (uint32_t i = 0; i < na; i++)
+    if ((shape->kinds[i] == AFX_ENC_PUBLIC_SCALAR || shape->kinds[i] == AFX_ENC_PUBLIC_POINT) && !b->attr_values) missing = true;
+  for (uint32_t e = 0; e < ne && !missing; e++) {
+    const afx_encproof_soa& q = b->enc[e];
+    missing |= !q.responses || !q.pk || !q.E1 || !q.E2 || !q.C_y_1 || !q.C_y_2 || !q.C_y_3 || !q.C_y_2p || !cm->enc[e];
+  }
+  if (missing) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
+  // one pass of staging for the whole call (the sliced, two-lane pipe of afx_verify_presentations is not built for this form)
+  Stager st(ctx);
+  auto in = [&](const uint8_t* p, size_t rows) { return st.add(p, rows * count * 32); };
+  const size_t o_rs = in(b->responses, nr), o_x0 = in(b->C_x_0, 1), o_x1 = in(b->C_x_1, 1), o_cv = in(b->C_V, 1), o_cy = in(b->C_y, na),
+               o_av = b->attr_values ? in(b->attr_values, na) : st.reserve(0), o_cm = in(cm->main, n_main);
+  std::vector<std::array<size_t, 9>> eo(ne);
+  for (uint32_t e = 0; e < ne; e++) {
+    const afx_encproof_soa& q = b->enc[e];
+    const uint8_t* f[9] = { cm->enc[e], q.responses, q.pk, q.E1, q.E2, q.C_y_1, q.C_y_2, q.C_y_3, q.C_y_2p };   // (slot 0: the commitments in the challenge's place)
+    for (int i = 0; i < 9; i++) eo[e][i] = in(f[i], i == 0 ? 5 : i == 1 ? 6 : 1);
+  }
+  const size_t o_st = st.add(nullptr, count);
+  int rc = st.upload();
+  if (rc) return rc;
+  std::vector<afx_encproof_soa> de(ne);
+  std::vector<uint8_t*> dc(ne);
+  for (uint32_t e = 0; e < ne; e++) {
+    de[e] = { nullptr, st.dev(eo[e][1]), st.dev(eo[e][2]), st.dev(eo[e][3]), st.dev(eo[e][4]), st.dev(eo[e][5]), st.dev(eo[e][6]), st.dev(eo[e][7]), st.dev(eo[e][8]) };
+    dc[e] = st.dev(eo[e][0]);
+  }
+  const afx_presentation_soa d = { nullptr, st.dev(o_rs), st.dev(o_x0), st.dev(o_x1), st.dev(o_cv), st.dev(o_cy), b->attr_values ? st.dev(o_av) : nullptr, de.data() };
+  const afx_commitments_soa dcm = { st.dev(o_cm), dc.data() };
+  if ((rc = afx_verify_presentations_batchable_dev(ctx, shape, &d, &dcm, weights, count, st.dev(o_st)))) return rc;
+  AFX_HIP(hipMemcpyAsync(status, st.dev(o_st), count, hipMemcpyDeviceToHost, st.stream()));
+  AFX_HIP(hipStreamSynchronize(st.stream()));
+  return AFX_OK;
 } catch (...) { return afx::exception_rc(); }
 
 extern "C" int afx_verify_encryption_proofs_dev(afx_ctx* ctx, uint16_t index, const afx_encproof_soa* batch, size_t count, uint8_t* status_dev) try {

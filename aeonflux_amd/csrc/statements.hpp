@@ -68,6 +68,22 @@ inline uint64_t mode_flags(const afx_ctx* c) {
          ((uint64_t)c->small_batch_items << 8) | ((uint64_t)(c->variants & 0x3f) << 40);   // (small_batch_items <= 2^16: bits 8-24)
 }
 
+// How many commitments the main proof of a presentation of this shape has in its batchable form (include/aeonflux_gpu.h): the
+// constraints Issuer::verify builds - Z = z*I, the one on C_x_1, one per kept commitment whose constraint-#3 position (the compact
+// index in the reference, the commitment's own position in strict mode) is not a hidden group element, and in strict mode one per
+// hidden group element at a position other than 0.  From the shape alone: whether a context refuses the shape is not asked here.
+inline uint32_t afx_batchable_n_main_of(const afx_shape& sh, bool strict) {
+  uint32_t k = 0, m = 2;
+  for (uint32_t i = 0; i < sh.n_attributes && i < AFX_MAX_ATTRIBUTES; i++) k += sh.kinds[i] != AFX_ENC_SECRET_POINT;
+  if (strict) {
+    m += k;
+    for (uint32_t e = 0; e < sh.n_enc_proofs && e < AFX_MAX_ATTRIBUTES; e++) m += sh.enc_indices[e] != 0;
+  } else {
+    for (uint32_t j = 0; j < k; j++) m += sh.kinds[j] != AFX_ENC_SECRET_POINT;
+  }
+  return m;
+}
+
 namespace afx {
 // internal return codes of the staging path (never leave the library)
 static constexpr int AFX_RETRY_FULL = -1000;       // the collecting session cannot take this call: wait for the next one

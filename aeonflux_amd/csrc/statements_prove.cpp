@@ -239,8 +239,9 @@ extern "C" int afx_issue_dev(afx_ctx* ctx, const afx_attributes_soa* requests, c
 // ------------------------------------------------------------------------------------------------
 // AnonymousCredential::show
 // ------------------------------------------------------------------------------------------------
-extern "C" int afx_show_dev(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keypairs_soa* keypairs, const afx_show_randomness* rnd,
-                            size_t count, const afx_presentation_out* out, afx_shape* shape_out, uint8_t* status_dev) try {
+// `cm` (the batchable form, include/aeonflux_gpu.h): the commitments every proof hashed are written out as well
+static int show_dev_impl(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keypairs_soa* keypairs, const afx_show_randomness* rnd,
+                         size_t count, const afx_presentation_out* out, const afx_commitments_soa* cm, afx_shape* shape_out, uint8_t* status_dev) {
   CtxLock lock__(ctx);
   if (!ctx || !creds || !rnd || !out || !shape_out || !status_dev) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   const afx_credentials_soa cr = *creds;
@@ -265,7 +266,15 @@ extern "C" int afx_show_dev(afx_ctx* ctx, const afx_credentials_soa* creds, cons
   sh.n_responses = 3 + hs;
   sh.n_enc_proofs = nsp;
   *shape_out = sh;
+  const uint32_t n_main = cm ? afx_batchable_main_commitments(ctx, &sh) : 0;
+  if (cm && !n_main) { set_error("this shape has no batchable form (every presentation of it is rejected)"); return AFX_E_BAD_ARGS; }
   if (count == 0) return AFX_OK;
+  if (cm && (!cm->main || (nsp && !cm->enc))) { set_error("null commitment array"); return AFX_E_BAD_ARGS; }
+  for (uint32_t e = 0; cm && e < nsp; e++)
+    if (!cm->enc[e]) { set_error("null commitment array"); return AFX_E_BAD_ARGS; }
+  std::vector<uint8_t*> cm_enc;
+  if (cm && nsp) cm_enc.assign(cm->enc, cm->enc + nsp);
+  uint8_t* const cm_main = cm ? cm->main : nullptr;
   if (nsp && (!cr.M2 || !cr.m3 || !out->enc)) { set_error("hidden group elements need M2, m3 and enc outputs"); return AFX_E_BAD_ARGS; }
   const bool no_key = nsp && !keypairs;   // CredentialError::NoSymmetricKey (:150-157)
   if (!no_key) {
@@ -288,7 +297,7 @@ extern "C" int afx_show_dev(afx_ctx* ctx, const afx_credentials_soa* creds, cons
   struct { uint32_t n; uint8_t kinds[AFX_MAX_ATTRIBUTES]; } kd__;
   memset(&kd__, 0, sizeof kd__);
   kd__.n = na; memcpy(kd__.kinds, cr.kinds, std::min<size_t>(na, AFX_MAX_ATTRIBUTES));
-  const PlanKey key__ = plan_key("show", &kd__, sizeof kd__, mode_flags(ctx) | (no_key ? 4u : 0u));
+  const PlanKey key__ = plan_key(cm ? "show_batchable" : "show", &kd__, sizeof kd__, mode_flags(ctx) | (no_key ? 4u : 0u));
   return run_chunked(ctx, count, [&](Assembler& as, size_t off, uint32_t cc) {
     afx_ctx* c = as.ctx;
     as.secret_scalars = true;   // z, the hidden attributes, the symmetric key, every blinding: afx_ctx_set_secret_independent_addressing
@@ -391,7 +400,13 @@ extern "C" int afx_show_dev(afx_ctx* ctx, const afx_credentials_soa* creds, cons
     std::vector<afx_hash_program> rng_hash, chal_hash;
     std::vector<afx_msm_job> commit;
     std::vector<afx_scalarop_job> resp, blind_products;   // (blinding * coefficient) of the bases a segmenting pass multiplies part by part
-    p.prove_compact(r.rng_seed + off * 32, orow(o.challenge, 0), orow(o.responses, 0), 32 * count, rng_hash, commit, chal_hash, resp, &blind_products);
+    std::vector<uint8_t*> R_main, R_enc(5);
+    if (cm_main) {
+      if (p.num_constraints() != n_main) throw std::logic_error("the prover's main proof and afx_batchable_main_commitments disagree");
+      for (uint32_t j = 0; j < n_main; j++) R_main.push_back(orow(cm_main, j));
+    }
+    p.prove_compact(r.rng_seed + off * 32, orow(o.challenge, 0), orow(o.responses, 0), 32 * count, rng_hash, commit, chal_hash, resp, &blind_products,
+                    cm_main ? R_main.data() : nullptr);
 
     // proofs of encryption, one per hidden group element, in attribute order (:293-309 -> encryption.rs:58-142)
     for (uint32_t e = 0; e < nsp; e++) {
@@ -472,7 +487,9 @@ extern "C" int afx_show_dev(afx_ctx* ctx, const afx_credentials_soa* creds, cons
       ep.constrain(C_y_2p, { { sa1, C_y_2 } });
       ep.constrain(E1, { { sa0, C_y_2 }, { sm3, C_y_2p }, { sz1, G_y_2 } });
       ep.constrain(C_y_3, { { sz, G_y_3 }, { sm3, G_m_3 } });
-      ep.prove_compact(r.enc_seeds + (e * count + off) * 32, orow(q.challenge, 0), orow(q.responses, 0), 32 * count, rng_hash, commit, chal_hash, resp, &blind_products);
+      if (cm_main) for (size_t j = 0; j < 5; j++) R_enc[j] = orow(cm_enc[e], j);
+      ep.prove_compact(r.enc_seeds + (e * count + off) * 32, orow(q.challenge, 0), orow(q.responses, 0), 32 * count, rng_hash, commit, chal_hash, resp, &blind_products,
+                       cm_main ? R_enc.data() : nullptr);
     }
     as.sccheck(sccheck);
     as.decode(decode);
@@ -488,6 +505,16 @@ extern "C" int afx_show_dev(afx_ctx* ctx, const afx_credentials_soa* creds, cons
     as.scalarop(resp);
     as.finish(status_dev + off, AFX_ST_VERIFICATION_FAILURE);
   }, key__);
+}
+extern "C" int afx_show_dev(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keypairs_soa* keypairs, const afx_show_randomness* rnd,
+                            size_t count, const afx_presentation_out* out, afx_shape* shape_out, uint8_t* status_dev) try {
+  return show_dev_impl(ctx, creds, keypairs, rnd, count, out, nullptr, shape_out, status_dev);
+} catch (...) { return afx::exception_rc(); }
+extern "C" int afx_show_batchable_dev(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keypairs_soa* keypairs, const afx_show_randomness* rnd,
+                                      size_t count, const afx_presentation_out* out, const afx_commitments_soa* commitments_out, afx_shape* shape_out,
+                                      uint8_t* status_dev) try {
+  if (!commitments_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  return show_dev_impl(ctx, creds, keypairs, rnd, count, out, commitments_out, shape_out, status_dev);
 } catch (...) { return afx::exception_rc(); }
 
 // ------------------------------------------------------------------------------------------------
@@ -591,9 +618,9 @@ extern "C" int afx_verify_issuances(afx_ctx* ctx, const afx_attributes_soa* attr
 
 // Credentials [first, first + n) of a host batch of `total` (AnonymousCredential::show, /root/reference/src/credential.rs:37-46);
 // every output array is indexed like the inputs.  shape_out is the same for every range of one batch.
-extern "C" int afx_show_range(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keypairs_soa* keypairs, const afx_show_randomness* rnd,
-                              size_t total, size_t first, size_t n, const afx_presentation_out* out, afx_shape* shape_out, uint8_t* status) try {
-  CtxLock lock__(ctx, true);
+static int show_range_impl(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keypairs_soa* keypairs, const afx_show_randomness* rnd,
+                           size_t total, size_t first, size_t n, const afx_presentation_out* out, const afx_commitments_soa* cm, afx_shape* shape_out, uint8_t* status) {
+  CtxLock lock__(ctx, !cm);   // (a batchable call takes the context in turn)
   if (!ctx || !creds || !rnd || !out || !shape_out || !status) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   const uint32_t na = creds->n_attributes;
   if (na == 0 || na > ctx->n) { set_error("credential attribute count does not fit the system parameters"); return AFX_E_BAD_ARGS; }
@@ -611,12 +638,26 @@ extern "C" int afx_show_range(afx_ctx* ctx, const afx_credentials_soa* creds, co
   if (n == 0) {   // the shape is still reported (an empty batch has one)
     afx_credentials_soa dc = *creds;
     afx_show_randomness dr = *rnd;
-    return afx_show_dev(ctx, &dc, kp ? keypairs : nullptr, &dr, 0, out, shape_out, status);
+    return show_dev_impl(ctx, &dc, kp ? keypairs : nullptr, &dr, 0, out, cm, shape_out, status);
+  }
+  // the batchable form: how many commitments the main proof has follows from the kinds.  An empty show_dev_impl call derives the shape
+  // from them (and refuses a shape without a batchable form) exactly as the real call will; it launches nothing and writes only *shape_out.
+  // (No join key below, so a small batchable show is assembled at every call: it takes the context in turn and is not collected.)
+  uint32_t n_main = 0;
+  if (cm) {
+    afx_shape sh0;
+    afx_credentials_soa dc = *creds;
+    afx_show_randomness dr = *rnd;
+    int rc0 = show_dev_impl(ctx, &dc, kp ? keypairs : nullptr, &dr, 0, out, cm, &sh0, status);
+    if (rc0) return rc0;
+    n_main = afx_batchable_main_commitments(ctx, &sh0);
+    if (!cm->main || (nsp && !cm->enc)) { set_error("null commitment array"); return AFX_E_BAD_ARGS; }
+    for (uint32_t e = 0; e < nsp; e++) if (!cm->enc[e]) { set_error("null commitment array"); return AFX_E_BAD_ARGS; }
   }
   struct { uint32_t n; uint8_t kinds[AFX_MAX_ATTRIBUTES]; } jd;
   memset(&jd, 0, sizeof jd);
   jd.n = na; memcpy(jd.kinds, creds->kinds, std::min<size_t>(na, AFX_MAX_ATTRIBUTES));
-  const PlanKey jkey = plan_key("S", &jd, sizeof jd, mode_flags(ctx) | (kp ? (uint64_t)1 << 63 : 0) | (out->attr_values ? (uint64_t)1 << 62 : 0));
+  const PlanKey jkey = cm ? PlanKey() : plan_key("S", &jd, sizeof jd, mode_flags(ctx) | (kp ? (uint64_t)1 << 63 : 0) | (out->attr_values ? (uint64_t)1 << 62 : 0));
   return host_pipe(ctx, n, [&](Stager& st, size_t off, size_t sn) -> int {
     const size_t f0 = first + off;
     const size_t dn = st.dev_items(sn);
@@ -639,6 +680,12 @@ extern "C" int afx_show_range(afx_ctx* ctx, const afx_credentials_soa* creds, co
                           out->enc[e].C_y_1, out->enc[e].C_y_2, out->enc[e].C_y_3, out->enc[e].C_y_2p };
       for (int f = 0; f < 9; f++) oe[e][f] = res(dst[f], f == 1 ? 6 : 1, 32);
     }
+    size_t o_cm = 0;
+    std::vector<size_t> o_ce(nsp);
+    if (cm) {
+      o_cm = res(cm->main, n_main, 32);
+      for (uint32_t e = 0; e < nsp; e++) o_ce[e] = res(cm->enc[e], 5, 32);
+    }
     int rc = st.upload();
     if (rc) return rc;
     afx_credentials_soa dc = *creds;
@@ -650,9 +697,22 @@ extern "C" int afx_show_range(afx_ctx* ctx, const afx_credentials_soa* creds, co
     for (uint32_t e = 0; e < nsp; e++)
       de[e] = { st.dev(oe[e][0]), st.dev(oe[e][1]), st.dev(oe[e][2]), st.dev(oe[e][3]), st.dev(oe[e][4]), st.dev(oe[e][5]), st.dev(oe[e][6]), st.dev(oe[e][7]), st.dev(oe[e][8]) };
     afx_presentation_out dout = { st.dev(o_ch), st.dev(o_rs), st.dev(o_x0), st.dev(o_x1), st.dev(o_cv), st.dev(o_cy), st.dev(o_av), de.data() };
-    if ((rc = afx_show_dev(ctx, &dc, kp ? &dk : nullptr, &dr, dn, &dout, shape_out, st.dev(o_st)))) return rc;
+    std::vector<uint8_t*> dce(nsp);
+    for (uint32_t e = 0; cm && e < nsp; e++) dce[e] = st.dev(o_ce[e]);
+    const afx_commitments_soa dcm = { cm ? st.dev(o_cm) : nullptr, dce.data() };
+    if ((rc = show_dev_impl(ctx, &dc, kp ? &dk : nullptr, &dr, dn, &dout, cm ? &dcm : nullptr, shape_out, st.dev(o_st)))) return rc;
     return st.fetch_all();
   }, jkey);
+}
+extern "C" int afx_show_range(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keypairs_soa* keypairs, const afx_show_randomness* rnd,
+                              size_t total, size_t first, size_t n, const afx_presentation_out* out, afx_shape* shape_out, uint8_t* status) try {
+  return show_range_impl(ctx, creds, keypairs, rnd, total, first, n, out, nullptr, shape_out, status);
+} catch (...) { return afx::exception_rc(); }
+extern "C" int afx_show_batchable(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keypairs_soa* keypairs, const afx_show_randomness* rnd,
+                                  size_t count, const afx_presentation_out* out, const afx_commitments_soa* commitments_out, afx_shape* shape_out,
+                                  uint8_t* status) try {
+  if (!commitments_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  return show_range_impl(ctx, creds, keypairs, rnd, count, 0, count, out, commitments_out, shape_out, status);
 } catch (...) { return afx::exception_rc(); }
 extern "C" int afx_show(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keypairs_soa* keypairs, const afx_show_randomness* rnd,
                         size_t count, const afx_presentation_out* out, afx_shape* shape_out, uint8_t* status) try {

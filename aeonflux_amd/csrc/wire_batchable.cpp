@@ -1,0 +1,382 @@
+// Batchable presentations on bytes (include/aeonflux_gpu.h "AFXB"): the header functions and the packer (host, bytes only) and the
+// two doors - afx_verify_presentations_batchable_wire (AFXB sections in, statuses out) and afx_show_batchable_wire (credentials in,
+// one AFXB section per group out).  Records are transposed on the GPU by the kernels the AFXP doors use (k_aos_to_soa,
+// k_soa_to_aos); the arithmetic is afx_verify_presentations_batchable_dev / afx_show_batchable_dev.  A batchable call takes the
+// context in turn: the groups of a request run one after the other, none is collected with other threads' calls.
+#include <string.h>
+#include <map>
+#include "statements.hpp"
+
+namespace {
+uint32_t rd32(const uint8_t* b) { return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24); }
+void wr32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
+bool shape_ok(const afx_shape& sh) {
+  if (sh.n_attributes > AFX_MAX_ATTRIBUTES || sh.n_responses > 3 + AFX_MAX_ATTRIBUTES || sh.n_hidden_scalars > AFX_MAX_ATTRIBUTES || sh.n_enc_proofs > AFX_MAX_ATTRIBUTES)
+    return false;
+  for (uint32_t i = 0; i < sh.n_attributes; i++)
+    if (sh.kinds[i] > AFX_ENC_SECRET_POINT) return false;
+  return true;
+}
+bool revealed(uint8_t kind) { return kind == AFX_ENC_PUBLIC_SCALAR || kind == AFX_ENC_PUBLIC_POINT; }
+// a main proof has the commitments of the reference's statement or of the strict one: nothing else is a well-formed header
+bool n_main_ok(const afx_shape& sh, uint32_t n_main) { return n_main == afx_batchable_n_main_of(sh, false) || n_main == afx_batchable_n_main_of(sh, true); }
+void write_header(uint8_t* h, size_t hdr, const afx_shape& sh, uint32_t n_main, uint32_t cells, size_t count) {
+  memset(h, 0, hdr);
+  memcpy(h, "AFXB", 4);
+  wr32(h + 4, 1); wr32(h + 8, (uint32_t)count); wr32(h + 12, cells);
+  wr32(h + 16, sh.n_attributes); wr32(h + 20, sh.n_responses); wr32(h + 24, sh.n_hidden_scalars); wr32(h + 28, sh.n_enc_proofs); wr32(h + 32, n_main);
+  uint8_t* p = h + 36;
+  for (uint32_t i = 0; i < sh.n_attributes; i++) *p++ = sh.kinds[i];
+  for (uint32_t i = 0; i < sh.n_hidden_scalars; i++) { *p++ = (uint8_t)sh.hidden_scalar_indices[i]; *p++ = (uint8_t)(sh.hidden_scalar_indices[i] >> 8); }
+  for (uint32_t i = 0; i < sh.n_enc_proofs; i++) { *p++ = (uint8_t)sh.enc_indices[i]; *p++ = (uint8_t)(sh.enc_indices[i] >> 8); }
+}
+// Rows of the struct-of-arrays scratch both doors use, in record order but for the revealed values:
+//   R[n_main] | responses[nr] | C_x_0 C_x_1 C_V | C_y[na] | per proof of encryption: R[5] responses[6] pk E1 E2 C_y_1 C_y_2 C_y_3 C_y_2p
+struct Rows {
+  uint32_t resp, cx, cy, enc, end;
+  Rows(const afx_shape& sh, uint32_t n_main) : resp(n_main), cx(resp + sh.n_responses), cy(cx + 3), enc(cy + sh.n_attributes), end(enc + 18 * sh.n_enc_proofs) {}
+};
+// cell -> row: the rows above, a revealed value's cell at values_row + its attribute position
+std::vector<uint32_t> cell_map(const afx_shape& sh, const Rows& R, uint32_t values_row) {
+  std::vector<uint32_t> m;
+  for (uint32_t r = 0; r < R.enc; r++) m.push_back(r);
+  for (uint32_t i = 0; i < sh.n_attributes; i++)
+    if (revealed(sh.kinds[i])) m.push_back(values_row + i);
+  for (uint32_t r = R.enc; r < R.end; r++) m.push_back(r);
+  return m;
+}
+}  // namespace
+
+extern "C" size_t afx_batchable_wire_header_bytes(const afx_shape* sh) {
+  if (!sh || !shape_ok(*sh)) return 0;
+  return (36 + sh->n_attributes + 2 * (size_t)sh->n_hidden_scalars + 2 * (size_t)sh->n_enc_proofs + 31) & ~size_t(31);
+}
+extern "C" uint32_t afx_batchable_wire_cells_per_record(const afx_shape* sh, uint32_t n_main_commitments) {
+  if (!sh || !shape_ok(*sh) || !n_main_ok(*sh, n_main_commitments)) return 0;
+  uint32_t pub = 0;
+  for (uint32_t i = 0; i < sh->n_attributes; i++) pub += revealed(sh->kinds[i]);
+  return n_main_commitments + sh->n_responses + 3 + sh->n_attributes + pub + 18 * sh->n_enc_proofs;
+}
+extern "C" int afx_batchable_wire_parse(const uint8_t* blob, size_t len, afx_shape* shape_out, uint32_t* n_main_out, size_t* count_out, size_t* records_offset_out) try {
+  if (!blob || !shape_out || !n_main_out || !count_out || !records_offset_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  if (len < 36 || memcmp(blob, "AFXB", 4) != 0 || rd32(blob + 4) != 1) { set_error("not an AFXB v1 batch"); return AFX_E_BAD_ARGS; }
+  afx_shape sh;
+  memset(&sh, 0, sizeof sh);
+  const uint32_t count = rd32(blob + 8), cells = rd32(blob + 12), n_main = rd32(blob + 32);
+  sh.n_attributes = rd32(blob + 16); sh.n_responses = rd32(blob + 20); sh.n_hidden_scalars = rd32(blob + 24); sh.n_enc_proofs = rd32(blob + 28);
+  if (sh.n_attributes > AFX_MAX_ATTRIBUTES || sh.n_responses > 3 + AFX_MAX_ATTRIBUTES || sh.n_hidden_scalars > AFX_MAX_ATTRIBUTES || sh.n_enc_proofs > AFX_MAX_ATTRIBUTES) {
+    set_error("shape field out of range");
+    return AFX_E_BAD_ARGS;
+  }
+  const size_t hdr = (36 + sh.n_attributes + 2 * (size_t)sh.n_hidden_scalars + 2 * (size_t)sh.n_enc_proofs + 31) & ~size_t(31);
+  if (len < hdr) { set_error("truncated header"); return AFX_E_BAD_ARGS; }
+  const uint8_t* p = blob + 36;
+  for (uint32_t i = 0; i < sh.n_attributes; i++) sh.kinds[i] = *p++;
+  for (uint32_t i = 0; i < sh.n_hidden_scalars; i++) { sh.hidden_scalar_indices[i] = (uint16_t)(p[0] | (p[1] << 8)); p += 2; }
+  for (uint32_t i = 0; i < sh.n_enc_proofs; i++) { sh.enc_indices[i] = (uint16_t)(p[0] | (p[1] << 8)); p += 2; }
+  if (!shape_ok(sh)) { set_error("attribute kind out of range"); return AFX_E_BAD_ARGS; }
+  if (!n_main_ok(sh, n_main)) { set_error("n_main_commitments does not match the shape"); return AFX_E_BAD_ARGS; }
+  if (cells != afx_batchable_wire_cells_per_record(&sh, n_main)) { set_error("cells_per_record does not match the shape"); return AFX_E_BAD_ARGS; }
+  if ((len - hdr) / 32 / cells < count || len != hdr + (size_t)count * cells * 32) { set_error("record area length"); return AFX_E_BAD_ARGS; }
+  *shape_out = sh; *n_main_out = n_main; *count_out = count; *records_offset_out = hdr;
+  return AFX_OK;
+} catch (...) { return afx::exception_rc(); }
+// the length of the section that starts at blob (its header names it); the section itself is checked by afx_batchable_wire_parse
+extern "C" int afx_batchable_wire_section_bytes(const uint8_t* blob, size_t len, size_t* section_len_out) try {
+  if (!blob || !section_len_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  if (len < 36 || memcmp(blob, "AFXB", 4) != 0 || rd32(blob + 4) != 1) { set_error("not an AFXB v1 batch"); return AFX_E_BAD_ARGS; }
+  const uint32_t count = rd32(blob + 8), cells = rd32(blob + 12), na = rd32(blob + 16), hs = rd32(blob + 24), ne = rd32(blob + 28);
+  if (na > AFX_MAX_ATTRIBUTES || hs > AFX_MAX_ATTRIBUTES || ne > AFX_MAX_ATTRIBUTES || cells == 0 || cells > 4096) { set_error("shape field out of range"); return AFX_E_BAD_ARGS; }
+  const size_t hdr = (36 + na + 2 * (size_t)hs + 2 * (size_t)ne + 31) & ~size_t(31);
+  const size_t sl = hdr + (size_t)count * cells * 32;
+  if (sl > len) { set_error("truncated section"); return AFX_E_BAD_ARGS; }
+  *section_len_out = sl;
+  return AFX_OK;
+} catch (...) { return afx::exception_rc(); }
+
+extern "C" int afx_batchable_wire_pack(const afx_shape* shape, const afx_presentation_soa* batch, const afx_commitments_soa* cm, uint32_t n_main, size_t count,
+                                       uint8_t* blob, size_t blob_cap, size_t* len_out) try {
+  if (!shape || !batch || !cm || !len_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  const size_t hdr = afx_batchable_wire_header_bytes(shape);
+  const uint32_t cells = afx_batchable_wire_cells_per_record(shape, n_main);
+  if (hdr == 0 || cells == 0 || count > 0xffffffffu) { set_error("shape or n_main_commitments out of range"); return AFX_E_BAD_ARGS; }
+  const size_t len = hdr + count * cells * 32;
+  *len_out = len;
+  if (!blob) return AFX_OK;   // size query
+  if (blob_cap < len) { set_error("blob buffer too small"); return AFX_E_BAD_ARGS; }
+  const afx_shape& sh = *shape;
+  const afx_presentation_soa& b = *batch;
+  bool missing = count && (!cm->main || !b.C_x_0 || !b.C_x_1 || !b.C_V || (sh.n_attributes && !b.C_y) || (sh.n_responses && !b.responses) || (sh.n_enc_proofs && (!b.enc || !cm->enc)));
+  for (uint32_t i = 0; i < sh.n_attributes; i++)
+    if (revealed(sh.kinds[i]) && count && !b.attr_values) missing = true;
+  for (uint32_t e = 0; e < sh.n_enc_proofs && !missing && count; e++) {
+    const afx_encproof_soa& q = b.enc[e];
+    missing |= !cm->enc[e] || !q.responses || !q.pk || !q.E1 || !q.E2 || !q.C_y_1 || !q.C_y_2 || !q.C_y_3 || !q.C_y_2p;
+  }
+  if (missing) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
+  write_header(blob, hdr, sh, n_main, cells, count);
+  std::vector<const uint8_t*> col;
+  auto rows = [&](const uint8_t* base, uint32_t k) { for (uint32_t r = 0; r < k; r++) col.push_back(base + (size_t)r * count * 32); };
+  rows(cm->main, n_main); rows(b.responses, sh.n_responses); rows(b.C_x_0, 1); rows(b.C_x_1, 1); rows(b.C_V, 1); rows(b.C_y, sh.n_attributes);
+  for (uint32_t i = 0; i < sh.n_attributes; i++)
+    if (revealed(sh.kinds[i])) col.push_back(b.attr_values + (size_t)i * count * 32);
+  for (uint32_t e = 0; e < sh.n_enc_proofs; e++) {
+    const afx_encproof_soa& q = b.enc[e];
+    rows(cm->enc[e], 5); rows(q.responses, 6); rows(q.pk, 1); rows(q.E1, 1); rows(q.E2, 1); rows(q.C_y_1, 1); rows(q.C_y_2, 1); rows(q.C_y_3, 1); rows(q.C_y_2p, 1);
+  }
+  if (col.size() != cells) { set_error("internal: wire cell list"); return AFX_E_BAD_ARGS; }
+  uint8_t* rec = blob + hdr;
+  for (size_t i = 0; i < count; i++)
+    for (uint32_t c = 0; c < cells; c++, rec += 32) memcpy(rec, col[c] + i * 32, 32);
+  return AFX_OK;
+} catch (...) { return afx::exception_rc(); }
+
+// ------------------------------------------------------------------------------------------------
+// the verifier's door
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct VSection { size_t first, n; const uint8_t* rec; };             // items [first, first + n) of the stream
+struct VGroup { afx_shape sh; uint32_t n_main, cells; std::vector<VSection> secs; size_t total = 0; };
+
+// one merged group: its sections' records gathered into one staged array, transposed, verified as one column call
+int verify_group(afx_ctx* ctx, const VGroup& G, const afx_device_rng& rng, uint8_t* status) {
+  AFX_HIP(hipSetDevice(ctx->device));
+  const uint32_t expect = afx_batchable_main_commitments(ctx, &G.sh);
+  if (expect == 0) {   // a shape every item fails on: answered without reading a record
+    for (const VSection& s : G.secs) memset(status + s.first, AFX_ST_VERIFICATION_FAILURE, s.n);
+    return AFX_OK;
+  }
+  const afx_shape& sh = G.sh;
+  const Rows R(sh, G.n_main);
+  const uint32_t values_row = R.end, rows = values_row + sh.n_attributes;
+  const std::vector<uint32_t> map = cell_map(sh, R, values_row);
+  if (map.size() != G.cells) { set_error("internal: AFXB cell map"); return AFX_E_BAD_ARGS; }
+  const size_t n = G.total;
+  std::vector<Stager::Piece> pieces;
+  size_t at = 0;
+  for (const VSection& s : G.secs) { pieces.push_back({ at, s.n, s.rec }); at += s.n; }
+  Stager st(ctx);
+  const size_t o_rec = st.add_rows_pieces(pieces, (size_t)G.cells * 32, n, 0, n, n), o_map = st.add((const uint8_t*)map.data(), 4 * map.size()),
+               o_soa = st.reserve(n * rows * 32), o_st = st.add(nullptr, n);
+  int rc = st.upload();
+  if (rc) return rc;
+  AFX_HIP(afxk_aos_to_soa(st.stream(), st.dev(o_rec), st.dev(o_soa), (const uint32_t*)st.dev(o_map), G.cells, (uint32_t)n));
+  auto rowp = [&](uint32_t r) { return st.dev(o_soa) + (size_t)r * n * 32; };
+  std::vector<afx_encproof_soa> encs(sh.n_enc_proofs);
+  std::vector<uint8_t*> cenc(sh.n_enc_proofs);
+  for (uint32_t e = 0; e < sh.n_enc_proofs; e++) {
+    const uint32_t r = R.enc + 18 * e;
+    cenc[e] = rowp(r);
+    encs[e] = { nullptr, rowp(r + 5), rowp(r + 11), rowp(r + 12), rowp(r + 13), rowp(r + 14), rowp(r + 15), rowp(r + 16), rowp(r + 17) };
+  }
+  const afx_presentation_soa d = { nullptr, rowp(R.resp), rowp(R.cx), rowp(R.cx + 1), rowp(R.cx + 2), rowp(R.cy), rowp(values_row), encs.data() };
+  const afx_commitments_soa dcm = { rowp(0), cenc.data() };
+  if ((rc = afx_verify_presentations_batchable_dev(ctx, &sh, &d, &dcm, &rng, n, st.dev(o_st)))) return rc;
+  std::vector<uint8_t> got(n);
+  AFX_HIP(hipMemcpyAsync(got.data(), st.dev(o_st), n, hipMemcpyDeviceToHost, st.stream()));
+  AFX_HIP(hipStreamSynchronize(st.stream()));
+  at = 0;
+  for (const VSection& s : G.secs) { memcpy(status + s.first, got.data() + at, s.n); at += s.n; }
+  return AFX_OK;
+}
+}  // namespace
+
+extern "C" int afx_verify_presentations_batchable_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, const afx_device_rng* weights, uint8_t* status,
+                                                       size_t status_cap, size_t* count_out) try {
+  CtxLock lock__(ctx);
+  if (!ctx || !blob || !count_out || (!status && status_cap)) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  // every section is parsed before anything runs: a malformed one anywhere fails the call with nothing written
+  std::vector<VGroup> groups;
+  std::map<std::string, size_t> by_shape;
+  size_t off = 0, total = 0;
+  while (off < len) {
+    size_t sl = 0, cnt = 0, rec = 0;
+    afx_shape sh;
+    uint32_t n_main = 0;
+    int rc = afx_batchable_wire_section_bytes(blob + off, len - off, &sl);
+    if (!rc) rc = afx_batchable_wire_parse(blob + off, sl, &sh, &n_main, &cnt, &rec);
+    if (rc) { set_error("section at byte " + std::to_string(off) + ": " + afx_last_error()); return rc; }
+    const uint32_t expect = afx_batchable_main_commitments(ctx, &sh);
+    if (expect && expect != n_main) { set_error("section at byte " + std::to_string(off) + ": n_main_commitments is not what this context verifies for the shape"); return AFX_E_BAD_ARGS; }
+    const afx_shape csh = canonical_shape(sh);
+    std::string key((const char*)&csh, sizeof csh);
+    key.append((const char*)&n_main, sizeof n_main);
+    auto it = by_shape.find(key);
+    if (it == by_shape.end()) {
+      it = by_shape.emplace(key, groups.size()).first;
+      VGroup g;
+      g.sh = sh; g.n_main = n_main; g.cells = afx_batchable_wire_cells_per_record(&sh, n_main);
+      groups.push_back(g);
+    }
+    if (cnt) { groups[it->second].secs.push_back({ total, cnt, blob + off + rec }); groups[it->second].total += cnt; }
+    total += cnt;
+    off += sl;
+  }
+  *count_out = total;
+  if (total == 0) return AFX_OK;
+  if (status_cap < total) { set_error("status buffer too small"); return AFX_E_BAD_ARGS; }
+  if (total > 0xffffffffu / 64) { set_error("stream too large for one call"); return AFX_E_BAD_ARGS; }
+  if (!ctx->has_key) { set_error("Issuer::verify needs the issuer key"); return AFX_E_NO_KEY; }
+  // one seed for the call (the caller's, or the library's own); every merged group draws under its own stream number
+  uint8_t seed[32];
+  afx_device_rng base = { nullptr, 0 };
+  if (weights) base = *weights;
+  if (!base.seed) {
+    DrawSeed own;
+    const afx_device_rng none = { nullptr, base.stream };
+    int rc = own.init(&none);
+    if (rc) return rc;
+    memcpy(seed, own.b, 32);
+    base.seed = seed;
+  }
+  int rc = AFX_OK;
+  for (size_t g = 0; g < groups.size() && !rc; g++) {
+    if (!groups[g].total) continue;
+    const afx_device_rng rng = { base.seed, base.stream + g };
+    rc = verify_group(ctx, groups[g], rng, status);
+  }
+  afx::afx_wipe(seed, sizeof seed);
+  return rc;
+} catch (...) { return afx::exception_rc(); }
+
+// ------------------------------------------------------------------------------------------------
+// the user's door
+// ------------------------------------------------------------------------------------------------
+namespace {
+afx_shape shape_of_credentials(const afx_credentials_soa& cr) {
+  afx_shape sh;
+  memset(&sh, 0, sizeof sh);
+  sh.n_attributes = cr.n_attributes;
+  uint32_t hs = 0, nsp = 0;
+  for (uint32_t i = 0; i < cr.n_attributes; i++) {
+    switch (cr.kinds[i]) {
+      case AFX_ATTR_PUBLIC_SCALAR: sh.kinds[i] = AFX_ENC_PUBLIC_SCALAR; break;
+      case AFX_ATTR_SECRET_SCALAR: sh.kinds[i] = AFX_ENC_SECRET_SCALAR; sh.hidden_scalar_indices[hs++] = (uint16_t)i; break;
+      case AFX_ATTR_SECRET_POINT: sh.kinds[i] = AFX_ENC_SECRET_POINT; sh.enc_indices[nsp++] = (uint16_t)i; break;
+      default: sh.kinds[i] = AFX_ENC_PUBLIC_POINT; break;
+    }
+  }
+  sh.n_hidden_scalars = hs; sh.n_responses = 3 + hs; sh.n_enc_proofs = nsp;
+  return sh;
+}
+struct BJob { afx_shape sh; uint32_t n_main = 0, cells = 0; size_t out_off = 0, hdr = 0; bool no_key = false; };
+
+// one group: afx_show_batchable_dev writes into the rows of a scratch region, the credential's value rows are staged right behind it
+// (a revealed value's cell reads its value row), k_soa_to_aos makes the records (failed items zeroed), fetched in one piece
+int show_group(afx_ctx* ctx, const afx_show_group& G, const BJob& J, uint8_t* rec_out, uint8_t* status) {
+  AFX_HIP(hipSetDevice(ctx->device));
+  const afx_credentials_soa& cr = G.creds;
+  const afx_shape& sh = J.sh;
+  const size_t n = G.count;
+  const uint32_t na = sh.n_attributes, nsp = sh.n_enc_proofs;
+  const bool kp = G.keypairs && nsp;
+  const Rows R(sh, J.n_main);
+  const uint32_t chal = R.end, values_row = (chal + 1 + nsp + 7) & ~7u;   // the compact challenges (written, not sent), then pad: values_row * n * 32 is a multiple of 256
+  const std::vector<uint32_t> map = cell_map(sh, R, values_row);
+  if (map.size() != J.cells) { set_error("internal: AFXB show cell map"); return AFX_E_BAD_ARGS; }
+  Stager st(ctx);
+  auto in = [&](const uint8_t* p, size_t k, size_t elem) { return st.add(p, k * n * elem); };
+  const size_t o_soa = st.reserve(n * values_row * 32), o_val = in(cr.values, na, 32), o_map = st.add((const uint8_t*)map.data(), 4 * map.size());
+  const size_t o_M2 = nsp ? in(cr.M2, na, 32) : 0, o_m3 = nsp ? in(cr.m3, na, 32) : 0, o_t = in(cr.t, 1, 32), o_U = in(cr.U, 1, 32), o_V = in(cr.V, 1, 32);
+  const size_t o_zw = in(G.rnd.z_wide, 1, 64), o_seed = in(G.rnd.rng_seed, 1, 32), o_es = nsp ? in(G.rnd.enc_seeds, nsp, 32) : 0;
+  size_t o_kp[4] = { 0, 0, 0, 0 };
+  if (kp) { o_kp[0] = in(G.keypairs->a, 1, 32); o_kp[1] = in(G.keypairs->a0, 1, 32); o_kp[2] = in(G.keypairs->a1, 1, 32); o_kp[3] = in(G.keypairs->pk, 1, 32); }
+  const size_t o_out = st.add(nullptr, n * J.cells * 32), o_st = st.add(nullptr, n);
+  int rc = st.upload();
+  if (rc) return rc;
+  uint8_t* soa_d = st.dev(o_soa);
+  if (st.dev(o_val) != soa_d + (size_t)values_row * n * 32) { set_error("internal: value rows are not behind the show scratch"); return AFX_E_BAD_ARGS; }
+  auto rowp = [&](uint32_t r) { return soa_d + (size_t)r * n * 32; };
+  afx_credentials_soa dc = cr;
+  dc.values = st.dev(o_val); dc.M2 = nsp ? st.dev(o_M2) : nullptr; dc.m3 = nsp ? st.dev(o_m3) : nullptr;
+  dc.t = st.dev(o_t); dc.U = st.dev(o_U); dc.V = st.dev(o_V);
+  const afx_keypairs_soa dk = { st.dev(o_kp[0]), st.dev(o_kp[1]), st.dev(o_kp[2]), st.dev(o_kp[3]) };
+  const afx_show_randomness dr = { st.dev(o_zw), st.dev(o_seed), nsp ? st.dev(o_es) : nullptr };
+  std::vector<afx_encproof_out> de(nsp);
+  std::vector<uint8_t*> ce(nsp);
+  for (uint32_t e = 0; e < nsp; e++) {
+    const uint32_t r = R.enc + 18 * e;
+    ce[e] = rowp(r);
+    de[e] = { rowp(chal + 1 + e), rowp(r + 5), rowp(r + 11), rowp(r + 12), rowp(r + 13), rowp(r + 14), rowp(r + 15), rowp(r + 16), rowp(r + 17) };
+  }
+  const afx_presentation_out dout = { rowp(chal), rowp(R.resp), rowp(R.cx), rowp(R.cx + 1), rowp(R.cx + 2), rowp(R.cy), nullptr, nsp ? de.data() : nullptr };
+  const afx_commitments_soa dcm = { rowp(0), ce.data() };
+  afx_shape shape_dev;
+  if ((rc = afx_show_batchable_dev(ctx, &dc, kp ? &dk : nullptr, &dr, n, &dout, &dcm, &shape_dev, st.dev(o_st)))) return rc;
+  AFX_HIP(afxk_soa_to_aos(st.stream(), soa_d, st.dev(o_out), (const uint32_t*)st.dev(o_map), st.dev(o_st), J.cells, (uint32_t)n));
+  AFX_HIP(hipMemcpyAsync(rec_out, st.dev(o_out), n * J.cells * 32, hipMemcpyDeviceToHost, st.stream()));
+  AFX_HIP(hipMemcpyAsync(status, st.dev(o_st), n, hipMemcpyDeviceToHost, st.stream()));
+  AFX_HIP(hipStreamSynchronize(st.stream()));
+  return AFX_OK;
+}
+}  // namespace
+
+extern "C" int afx_show_batchable_wire(afx_ctx* ctx, afx_show_group* groups, size_t n_groups, uint8_t* out, size_t out_cap, size_t* out_len, uint8_t* status,
+                                       size_t status_len) try {
+  CtxLock lock__(ctx);
+  if (!ctx || !out_len || (!groups && n_groups)) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  std::vector<BJob> jobs(n_groups);
+  size_t total_len = 0, items = 0;
+  for (size_t gi = 0; gi < n_groups; gi++) {
+    const afx_show_group& G = groups[gi];
+    const afx_credentials_soa& cr = G.creds;
+    BJob& J = jobs[gi];
+    auto bad = [&](const char* why) { set_error("group " + std::to_string(gi) + ": " + why); return AFX_E_BAD_ARGS; };
+    if (cr.n_attributes == 0 || cr.n_attributes > ctx->n) return bad("credential attribute count does not fit the system parameters");
+    for (uint32_t i = 0; i < cr.n_attributes; i++)
+      if (cr.kinds[i] > AFX_ATTR_SECRET_POINT) return bad("unknown attribute kind");
+    if (G.count > 0xffffffffu / 64) return bad("too many credentials in one group");
+    J.sh = shape_of_credentials(cr);
+    J.n_main = afx_batchable_main_commitments(ctx, &J.sh);
+    if (!J.n_main) return bad("this shape has no batchable form (every presentation of it is rejected)");
+    J.cells = afx_batchable_wire_cells_per_record(&J.sh, J.n_main);
+    J.hdr = afx_batchable_wire_header_bytes(&J.sh);
+    const uint32_t nsp = J.sh.n_enc_proofs;
+    J.no_key = nsp && !G.keypairs;
+    if (out && G.count) {
+      if (!cr.values || !cr.t || !cr.U || !cr.V || !G.rnd.z_wide || !G.rnd.rng_seed || (nsp && (!G.rnd.enc_seeds || !cr.M2 || !cr.m3))) return bad("null batch array");
+      if (G.keypairs && nsp && (!G.keypairs->a || !G.keypairs->a0 || !G.keypairs->a1 || !G.keypairs->pk)) return bad("null keypair array");
+    }
+    J.out_off = total_len;
+    total_len += J.hdr + G.count * J.cells * 32;
+    items += G.count;
+  }
+  *out_len = total_len;
+  if (out) {
+    if (out_cap < total_len) { set_error("output buffer too small"); return AFX_E_BAD_ARGS; }
+    if (!status && status_len) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+    // positions given: each < status_len and used once over all groups; not given: contiguous after the groups before
+    std::vector<uint8_t> used(status_len, 0);
+    size_t next = 0;
+    for (size_t g = 0; g < n_groups; g++) {
+      for (size_t i = 0; i < groups[g].count; i++) {
+        const uint64_t p = groups[g].positions ? groups[g].positions[i] : (uint64_t)(next + i);
+        if (p >= status_len) { set_error("group " + std::to_string(g) + ": position outside the status array"); return AFX_E_BAD_ARGS; }
+        if (used[p]) { set_error("group " + std::to_string(g) + ": a status position is used twice"); return AFX_E_BAD_ARGS; }
+        used[p] = 1;
+      }
+      next += groups[g].count;
+    }
+  }
+  for (size_t g = 0; g < n_groups; g++) groups[g].shape_out = jobs[g].sh;
+  if (!out) return AFX_OK;   // size query: shapes and length only
+  size_t next = 0;
+  for (size_t g = 0; g < n_groups; g++) {
+    const afx_show_group& G = groups[g];
+    const BJob& J = jobs[g];
+    const size_t count = G.count;
+    uint8_t* h = out + J.out_off;
+    write_header(h, J.hdr, J.sh, J.n_main, J.cells, count);
+    std::vector<uint8_t> st_buf(count, AFX_ST_VERIFICATION_FAILURE);
+    if (J.no_key) {   // CredentialError::NoSymmetricKey, as afx_show answers it: zero records
+      memset(h + J.hdr, 0, count * J.cells * 32);
+      memset(st_buf.data(), AFX_ST_NO_SYMMETRIC_KEY, count);
+    } else if (count) {
+      const int rc = show_group(ctx, G, J, h + J.hdr, st_buf.data());
+      if (rc) return rc;
+    }
+    for (size_t i = 0; i < count; i++) status[G.positions ? G.positions[i] : next + i] = st_buf[i];
+    next += count;
+  }
+  return AFX_OK;
+} catch (...) { return afx::exception_rc(); }

@@ -290,3 +290,110 @@ def issue_wire_rng(ctx, blob, seed=None, stream=0):
     status = np.full(max(1, cnt.value), 255, np.uint8)
     check(fn(ctx.h, blob, len(blob), C.byref(rng), out.ctypes.data, out.size, C.byref(out_len), status.ctypes.data, status.size, C.byref(cnt)))
     return out[:out_len.value].tobytes(), status[:cnt.value]
+
+
+# ---- batchable presentations ("AFXB" v1: every challenge replaced by the proof's commitments) ------
+def batchable_header(shape, n_main, count):
+    n, nr, hs, ne = shape.n_attributes, shape.n_responses, shape.n_hidden_scalars, shape.n_enc_proofs
+    pub = sum(1 for i in range(n) if shape.kinds[i] in (0, 2))
+    cells = n_main + nr + 3 + n + pub + 18 * ne
+    h = b"AFXB" + struct.pack("<8I", 1, count, cells, n, nr, hs, ne, n_main)
+    h += bytes(shape.kinds[:n])
+    h += b"".join(struct.pack("<H", shape.hidden_scalar_indices[i]) for i in range(hs))
+    h += b"".join(struct.pack("<H", shape.enc_indices[i]) for i in range(ne))
+    h += bytes(-len(h) % 32)
+    return h, cells
+
+
+def pack_batchable(shape, p, cm):
+    """SoA presentation dict and commitments dict(main [n_main,count,32], enc [[5,count,32] per proof]) -> AFXB bytes"""
+    count = p["responses"].shape[1]
+    n, n_main = shape.n_attributes, cm["main"].shape[0]
+    cols = [cm["main"], p["responses"], p["C_x_0"][None], p["C_x_1"][None], p["C_V"][None], p["C_y"]]
+    cols += [p["attr_values"][i][None] for i in range(n) if shape.kinds[i] in (0, 2)]
+    for d, c in zip(p["enc"], cm["enc"]):
+        cols += [c] + [d[f] if d[f].ndim == 3 else d[f][None] for f in ENC_ORDER[1:]]
+    soa = np.concatenate([np.asarray(c, dtype=np.uint8) for c in cols], axis=0)      # [cells, count, 32]
+    h, cells = batchable_header(shape, n_main, count)
+    assert soa.shape == (cells, count, 32)
+    return h + np.ascontiguousarray(soa.transpose(1, 0, 2)).tobytes()
+
+
+def unpack_batchable(blob):
+    """AFXB bytes -> (Shape, SoA presentation dict without challenges, commitments dict)"""
+    assert blob[:4] == b"AFXB"
+    ver, count, cells, n, nr, hs, ne, n_main = struct.unpack("<8I", blob[4:36])
+    assert ver == 1
+    shape = Shape()
+    shape.n_attributes, shape.n_responses, shape.n_hidden_scalars, shape.n_enc_proofs = n, nr, hs, ne
+    o = 36
+    for i in range(n):
+        shape.kinds[i] = blob[o + i]
+    o += n
+    for i in range(hs):
+        shape.hidden_scalar_indices[i] = struct.unpack("<H", blob[o:o + 2])[0]
+        o += 2
+    for i in range(ne):
+        shape.enc_indices[i] = struct.unpack("<H", blob[o:o + 2])[0]
+        o += 2
+    o = (o + 31) & ~31
+    rec = np.frombuffer(blob, dtype=np.uint8, offset=o, count=count * cells * 32).reshape(count, cells, 32).transpose(1, 0, 2)
+    it = iter(range(cells))
+    take = lambda k: np.ascontiguousarray(np.stack([rec[next(it)] for _ in range(k)])) if k else np.zeros((0, count, 32), np.uint8)
+    cm = {"main": take(n_main), "enc": []}
+    p = {"challenge": None, "responses": take(nr), "C_x_0": take(1)[0], "C_x_1": take(1)[0], "C_V": take(1)[0], "C_y": take(n)}
+    av = np.zeros((n, count, 32), np.uint8)
+    for i in range(n):
+        if shape.kinds[i] in (0, 2):
+            av[i] = take(1)[0]
+    p["attr_values"] = av
+    p["enc"] = []
+    for _ in range(ne):
+        cm["enc"].append(take(5))
+        d = {"challenge": None}
+        d.update({f: (take(6) if f == "responses" else take(1)[0]) for f in ENC_ORDER[1:]})
+        p["enc"].append(d)
+    return shape, p, cm
+
+
+def verify_batchable_wire(ctx, blob, seed=None, stream=0):
+    """afx_verify_presentations_batchable_wire: statuses of a stream of AFXB sections, in stream order.  seed: 32 bytes for a
+    reproducible run; None: the library reads one from getrandom."""
+    import ctypes as C
+    from . import check, lib
+    n = C.c_size_t(0)
+    cap = max(1, len(blob) // 32)
+    status = np.full(cap, 255, np.uint8)
+    rng = _device_rng(seed, stream)
+    check(lib().afx_verify_presentations_batchable_wire(ctx.h, blob, len(blob), C.byref(rng), status.ctypes.data, cap, C.byref(n)))
+    return status[:n.value]
+
+
+def show_batchable_wire(ctx, items):
+    """afx_show_batchable_wire: AnonymousCredential::show into AFXB bytes.  items as for batch.show_mixed.
+    Returns (one AFXB section per item, back to back; [Shape per item]; status in the caller's order)."""
+    import ctypes as C
+    from . import ShowGroup, check, lib
+    from .batch import _positions, _show_args
+    arr = (ShowGroup * max(1, len(items)))()
+    keep, counts = [], []
+    for g, it in enumerate(items):
+        cs, kp, rnd, _, _, cnt, k = _show_args(it["kinds"], it["values"], it["t"], it["U"], it["V"], it.get("keypairs"), it["z_wide"], it["rng_seed"],
+                                               it.get("enc_seeds"), it.get("M2"), it.get("m3"), outputs=False)
+        arr[g].creds, arr[g].rnd, arr[g].count = cs, rnd, cnt
+        if kp is not None:
+            arr[g].keypairs = C.pointer(kp)
+        keep.append((k, kp))
+        counts.append(cnt)
+    pos, total = _positions(list(zip(items, counts)))
+    total = max([total] + [int(p.max()) + 1 for p in pos if p.size])
+    for g, p in enumerate(pos):
+        arr[g].positions = p.ctypes.data_as(C.POINTER(C.c_uint64))
+    fn = lib().afx_show_batchable_wire
+    out_len = C.c_size_t(0)
+    check(fn(ctx.h, arr, len(items), None, 0, C.byref(out_len), None, 0))
+    out = np.zeros(max(1, out_len.value), np.uint8)
+    status = np.full(max(1, total), 255, np.uint8)
+    check(fn(ctx.h, arr, len(items), out.ctypes.data, out.size, C.byref(out_len), status.ctypes.data, total))
+    shapes = [Shape.from_buffer_copy(bytes(arr[g].shape_out)) for g in range(len(items))]
+    return out[:out_len.value].tobytes(), shapes, status[:total]

@@ -717,6 +717,101 @@ int afx_show_wire_rng(afx_ctx* ctx, afx_show_group* groups, size_t n_groups, con
 int afx_group_show_wire_rng(afx_group* group, afx_show_group* groups, size_t n_groups, const afx_device_rng* rng, uint8_t* out,
                             size_t out_cap, size_t* out_len, uint8_t* status, size_t status_len);
 
+/* ---- Batchable presentation proofs -------------------------------------------------------------
+ * zkp's toolbox has two encodings of one proof: CompactProof { challenge, responses } (Prover::prove_compact, what the crate sends
+ * today) and BatchableProof { commitments, responses } (Prover::prove_batchable / Verifier::verify_batchable): the prover sends the
+ * commitments it hashed instead of the challenge it got.  Transcript, statement, labels and responses are the same.  Off unless
+ * called: nothing above changes.
+ *
+ * Semantics (normative).  A batchable presentation is a compact one with every `challenge` - of the main proof and of each proof of
+ * encryption - replaced by that proof's commitments R_0 .. R_(m-1), 32-byte ristretto255 encodings in constraint order.  m is the
+ * number of constraints the verifier builds for the shape: afx_batchable_main_commitments() for the main proof (2 + one per kept
+ * commitment whose constraint-#3 position is not a hidden group element, + in strict mode one per hidden group element at a position
+ * other than 0), 5 for a proof of encryption.  An item's status is AFX_ST_OK iff
+ *  1. everything afx_verify_presentations checks before a transcript holds unchanged (canonical scalars, decodable points, the shapes
+ *     the reference would panic on, an identity generator, strict-mode pairing);
+ *  2. every commitment decodes and none is the identity encoding (32 zero bytes): zkp's validate_and_append_blinding_commitment;
+ *  3. with c = the transcript's challenge after the received commitments were appended as its "blindcom" values, every constraint
+ *     holds as an equation of group elements:  R_j = sum_s resp_s * P_(j,s) - c * LHS_j.
+ * Hence (R, resp) is accepted iff the compact proof (c(R), resp) is accepted by afx_verify_presentations AND its recomputed
+ * commitments encode to exactly R.
+ *
+ * The engine checks 3 with ONE sum per item, over the main proof and all the proofs of encryption together:
+ *     sum_j rho_j * ( sum_s resp_s * P_(j,s) - c * LHS_j - R_j ) == identity.
+ *  - The weights rho_j are 128 bits each, one per (item, proof, constraint), unpredictable to whoever made the proofs.  A false accept
+ *    has probability at most 2^-128 per item.
+ *  - "identity" is the ristretto255 identity - any of the four Edwards points of its coset (X == 0 or Y == 0), not only (0, 1) - with
+ *    no cofactor multiplication: the sum is encoded and the encoding compared with 32 zero bytes.
+ *  - Weights (normative bytes): item `index` = its ordinal in the call draws
+ *        draw(seed, stream, index, AFX_DRAW_BATCH_WEIGHTS)   squeezed to 16 * M bytes (SHAKE256 over as many blocks as that takes),
+ *    M = n_main + 5 * n_enc_proofs; weight w (main proof's constraints first, then proof of encryption 0's five, ...) is bytes
+ *    [16 w, 16 w + 16) as a little-endian integer.  The label is not reachable through afx_rng_expand.
+ *  - `weights` NULL, or a NULL seed: the library reads a seed from getrandom(2) per call (what a server uses); a given seed makes a run
+ *    reproducible (tests).  A verifier whose seed the prover can predict has no soundness beyond the prover's honesty.  The library
+ *    zeroes its copies of the seed (a pinned image and the device's) as soon as the weights are drawn; for that the *_dev form waits
+ *    for the seed's copy, which is queued behind the lane's earlier work.
+ *  - Z = C_V - W - x0*C_x0 - ... stays its own multiscalar job on the issuer key exactly as in afx_verify_presentations and enters the
+ *    sum as a per-item base; every scalar of the sum itself is public, so the sum runs the fast tables in every secret mode:
+ *    afx_ctx_set_fixed_key_schedule and afx_ctx_set_secret_independent_addressing(1) govern the Z job only.
+ *  - A batchable call takes the context in turn (it is not collected with other threads' calls); the host-pointer forms stage a
+ *    call (the wire doors: a group) in one piece.  Statuses are per item: a failed item fails alone.
+ * afx_show_batchable writes everything afx_show writes (challenges included, byte for byte) plus the commitments: one call yields both
+ * encodings. */
+#define AFX_DRAW_BATCH_WEIGHTS 64u
+/* (declared apart from their typedefs, like afx_device_rng: the Rust shim does not bind them) */
+struct afx_commitments_soa {            /* the R_j of a batch; read by verify, written by show */
+  uint8_t* main;                        /* [n_main][count] Pt                                   */
+  uint8_t* const* enc;                  /* [n_enc_proofs] pointers, each [5][count] Pt           */
+};
+typedef struct afx_commitments_soa afx_commitments_soa;
+/* n_main under the context's strict setting; 0: every item of the shape fails (no commitment array is read) */
+uint32_t afx_batchable_main_commitments(const afx_ctx* ctx, const afx_shape* shape);
+/* batch->challenge and batch->enc[e].challenge are not read and may be NULL */
+int afx_verify_presentations_batchable(afx_ctx* ctx, const afx_shape* shape, const afx_presentation_soa* batch,
+                                       const afx_commitments_soa* commitments, const afx_device_rng* weights, size_t count, uint8_t* status);
+int afx_verify_presentations_batchable_dev(afx_ctx* ctx, const afx_shape* shape, const afx_presentation_soa* batch,
+                                           const afx_commitments_soa* commitments, const afx_device_rng* weights, size_t count,
+                                           uint8_t* status_dev);
+/* commitments_out->main must hold afx_batchable_main_commitments(ctx, shape_out) rows: size it from the credential kinds (2 + the
+ * attributes that are not hidden group elements in the reference's shapes; ask afx_batchable_main_commitments with the shape of an
+ * empty afx_show call when in doubt) */
+int afx_show_batchable(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keypairs_soa* keypairs, const afx_show_randomness* rnd,
+                       size_t count, const afx_presentation_out* out, const afx_commitments_soa* commitments_out, afx_shape* shape_out,
+                       uint8_t* status);
+int afx_show_batchable_dev(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keypairs_soa* keypairs, const afx_show_randomness* rnd,
+                           size_t count, const afx_presentation_out* out, const afx_commitments_soa* commitments_out, afx_shape* shape_out,
+                           uint8_t* status_dev);
+
+/* Batchable presentations on bytes: "AFXB" version 1 (a format of its own, not a version of AFXP, whose parsers stay as they are).
+ *   header  = "AFXB" | u32le 1 | u32le count | u32le cells_per_record | u32le n_attributes | u32le n_responses | u32le n_hidden_scalars
+ *             | u32le n_enc_proofs | u32le n_main_commitments | kinds[n_attributes] | u16le hidden_scalar_indices[] | u16le enc_indices[]
+ *             | zero padding to a multiple of 32 bytes  (the AFXP header's fields plus n_main_commitments)
+ *   record  = the AFXP record with `challenge` replaced by R[n_main_commitments] and each proof of encryption's `challenge` by R[5]:
+ *             R[n_main] | responses | C_x_0 C_x_1 C_V | C_y[n] | the revealed attribute values | per proof: R[5] responses[6] pk E1 E2
+ *             C_y_1 C_y_2 C_y_3 C_y_2p,  32-byte cells.
+ * The host-only functions accept as n_main_commitments what the shape's main proof has under the reference's statement or under the
+ * strict one and refuse anything else (AFX_E_BAD_ARGS, like a wrong magic, version, count, cell count, a truncated header or trailing
+ * bytes); the verifier's door also refuses a section whose n_main_commitments is not afx_batchable_main_commitments(ctx, shape). */
+size_t afx_batchable_wire_header_bytes(const afx_shape* shape);                                   /* 0: shape out of range */
+uint32_t afx_batchable_wire_cells_per_record(const afx_shape* shape, uint32_t n_main_commitments); /* 0: shape or n_main out of range */
+int afx_batchable_wire_parse(const uint8_t* blob, size_t len, afx_shape* shape_out, uint32_t* n_main_commitments_out, size_t* count_out,
+                             size_t* records_offset_out);
+int afx_batchable_wire_section_bytes(const uint8_t* blob, size_t len, size_t* section_len_out);
+/* host, bytes only; blob == NULL: the size query */
+int afx_batchable_wire_pack(const afx_shape* shape, const afx_presentation_soa* batch, const afx_commitments_soa* commitments,
+                            uint32_t n_main_commitments, size_t count, uint8_t* blob, size_t blob_cap, size_t* len_out);
+/* AFXB sections back to back, merged by shape; status[i] answers the i-th presentation of the stream.  The error contract of
+ * afx_verify_presentations_mixed_wire: a malformed section anywhere is AFX_E_BAD_ARGS and nothing is written; *count_out is set once
+ * the stream has parsed.  Weights: each merged group is one column call - its items draw at their ordinals within the group, the
+ * g-th group (in order of first appearance) under stream number weights->stream + g. */
+int afx_verify_presentations_batchable_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, const afx_device_rng* weights, uint8_t* status,
+                                            size_t status_cap, size_t* count_out);
+/* one AFXB section per group, the error contract of afx_show_wire: out == NULL is the size query (shapes and *out_len only), failed
+ * items are records of zeros, groups without the symmetric key they need get AFX_ST_NO_SYMMETRIC_KEY and zero records; a group whose
+ * shape has no batchable form fails the call. */
+int afx_show_batchable_wire(afx_ctx* ctx, afx_show_group* groups, size_t n_groups, uint8_t* out, size_t out_cap, size_t* out_len,
+                            uint8_t* status, size_t status_len);
+
 /* ---- setup helpers (cold path; still GPU arithmetic) ---------------------------------------- */
 
 /* IssuerParameters::generate (src/parameters.rs:349-362) and W = w*G_w (src/amacs.rs:104): given
