@@ -7,7 +7,11 @@
                                  commitments go into the transcript, the challenge comes out, and every constraint is compared as a
                                  group element.  The statements are not copied: pyref's own verify_presentation runs with its Verifier
                                  swapped for one whose verify_compact takes commitments;
-  weights(seed, stream, i, m)    the engine's weight draw restated with hashlib.
+  ref_verify_batchable_weighted  the same rules 1 and 2 and challenges, rule 3 as the header's ONE sum under weights the caller gives:
+                                 the only yardstick whose verdict depends on the weights' bytes;
+  weights(seed, stream, i, m)    the engine's weight draw restated with hashlib;
+  ShiftingProver, show_shifted,  pyref's prover with commitments R_j + e * D, hashed as sent, responses honest - and the shifts that make
+  cancelling_shifts              two false constraints cancel in the weighted sum under ONE item's weights (a forgery built to cancel).
 
 A batchable presentation here is a pair (p, cm): p a pyref presentation dict (its challenge fields are ignored), cm =
 dict(main=[32-byte R_j ...], enc=[[5 x R_j] per proof of encryption]).
@@ -20,6 +24,10 @@ from tests.pyref import statements as S
 from tests.pyref import zkp
 
 DRAW_BATCH_WEIGHTS = 64
+# the most triples in one coefficient job (plan.h afx_coef_job) of the 16-attribute layout SSSSSSSSPPPPEEEE, hidden [12..15], under the
+# strict statement - the base G_y[0]: its own position's constraint, -G_y[0] in the four DLEQ constraints, and G_y_1 of the four
+# proofs of encryption.  tests/test_hostsim_batchable.py reads it from the plan; tests/test_batchable_coef_on_host.py runs a job so long.
+LARGEST_COEF_JOB_16_STRICT = 9
 
 
 def pyref_presentation(p):
@@ -60,7 +68,8 @@ class _BatchableVerifier(zkp.Verifier):
     statement verifies its proofs; `trace` receives each proof's challenge (as 32 bytes)"""
     queue, trace = None, None
 
-    def verify_compact(self, challenge_ignored, responses):
+    def _challenge_of(self, responses):
+        """rules 1 and 2 for this proof and its transcript: (decoded statement points, received commitments, challenge)"""
         coms = type(self).queue.pop(0)
         if len(responses) != self.n_scalars:
             raise zkp.ProofError("wrong number of responses")
@@ -78,6 +87,10 @@ class _BatchableVerifier(zkp.Verifier):
             zkp._append_point(self.t, b"blindcom", self.labels[lhs], enc)
         c = zkp._challenge(self.t)
         type(self).trace.append(R.sc_bytes(c))
+        return pts, coms, c
+
+    def verify_compact(self, challenge_ignored, responses):
+        pts, coms, c = self._challenge_of(responses)
         for (lhs, terms), enc in zip(self.constraints, coms):
             want = R.msm([responses[s] for s, _ in terms] + [(-c) % R.L], [pts[p] for _, p in terms] + [pts[lhs]])
             if R.encode(want) != enc:
@@ -85,11 +98,47 @@ class _BatchableVerifier(zkp.Verifier):
         return list(coms)
 
 
+class _WeightedVerifier(_BatchableVerifier):
+    """the same proofs, rule 3 as the header's ONE sum: constraint j of the statement's proofs, counted through them in the order they
+    are verified, adds weights[j] * (sum_s resp_s P_(j,s) - c LHS_j - R_j) to `terms` (encoding -> [point, scalar]: the scalars of a
+    point that occurs more than once are added up mod l); nothing is compared here"""
+    weights, used, terms = None, 0, None
+
+    def verify_compact(self, challenge_ignored, responses):
+        cls = type(self)
+        pts, coms, c = self._challenge_of(responses)
+        if cls.used + len(coms) > len(cls.weights):
+            raise ValueError("fewer weights than the statement has constraints")
+
+        def add(enc, point, k):
+            t = cls.terms.setdefault(enc, [point, 0])
+            t[1] = (t[1] + k) % R.L
+        for (lhs, terms), enc in zip(self.constraints, coms):
+            w = cls.weights[cls.used]
+            cls.used += 1
+            for s, p in terms:
+                add(self.points[p], pts[p], w * responses[s])
+            add(self.points[lhs], pts[lhs], -w * c)
+            add(enc, R.decode(enc), -w)
+        return list(coms)
+
+
+def _sum_of(terms):
+    """sum k * P over [point, scalar] pairs with the doublings shared (pyref's msm doubles once per term)"""
+    acc = R.IDENTITY
+    for bit in range(max([k.bit_length() for _, k in terms] + [0]) - 1, -1, -1):
+        acc = R.add(acc, acc)
+        for P, k in terms:
+            if (k >> bit) & 1:
+                acc = R.add(acc, P)
+    return acc
+
+
 @contextlib.contextmanager
-def _batchable_statements(queue, trace):
+def _batchable_statements(queue, trace, verifier=_BatchableVerifier):
     saved = S.Verifier
-    _BatchableVerifier.queue, _BatchableVerifier.trace = queue, trace
-    S.Verifier = _BatchableVerifier
+    verifier.queue, verifier.trace = queue, trace
+    S.Verifier = verifier
     try:
         yield
     finally:
@@ -108,6 +157,29 @@ def ref_verify_batchable(params, key, ip, p, cm, strict=False, trace=None):
     return st
 
 
+def ref_verify_batchable_weighted(params, key, ip, p, cm, weights, strict=False, trace=None):
+    """the header's verdict under GIVEN weights (integers, weight w of the header's order at weights[w]): rules 1 and 2 and the
+    challenges exactly as ref_verify_batchable, then the one sum over the main proof and the proofs of encryption
+        sum_j weights[j] * (sum_s resp_s P_(j,s) - c LHS_j - R_j),
+    accepted iff it encodes to 32 zero bytes.  An item that passes rules 1 and 2 must meet exactly len(weights) constraints."""
+    q = dict(p, challenge=bytes(32), enc=[dict(e, challenge=bytes(32)) for e in p["enc"]])
+    queue = [list(cm["main"])] + [list(c) for c in cm["enc"]]
+    if len(cm["enc"]) != len(p["enc"]):
+        return S.VERIFICATION_FAILURE
+    V = _WeightedVerifier
+    V.weights, V.used, V.terms = [int(w) for w in weights], 0, {}
+    try:
+        with _batchable_statements(queue, trace if trace is not None else [], V):
+            st, _ = S.verify_presentation(params, key, ip, q, strict=strict)
+        if st != S.OK:
+            return st
+        if V.used != len(V.weights):
+            raise ValueError("%d weights for a statement of %d constraints" % (len(V.weights), V.used))
+        return S.OK if R.encode(_sum_of(list(V.terms.values()))) == bytes(32) else S.VERIFICATION_FAILURE
+    finally:
+        V.weights, V.used, V.terms = None, 0, None
+
+
 def weights(seed, stream, index, m, label=DRAW_BATCH_WEIGHTS):
     """the m 128-bit weights of item `index`: draw(seed, stream, index, label) squeezed to 16 m bytes, little-endian integers"""
     d = hashlib.shake_256(b"aeonflux-amd/device-rng/v1" + bytes(seed) + stream.to_bytes(8, "little") + index.to_bytes(8, "little") + bytes([label])).digest(16 * m)
@@ -119,3 +191,90 @@ def arrays_of(cms):
     import numpy as np
     col = lambda rows: np.stack([np.stack([np.frombuffer(r, np.uint8) for r in item]) for item in rows], axis=1).copy()
     return dict(main=col([c["main"] for c in cms]), enc=[col([c["enc"][e] for c in cms]) for e in range(len(cms[0]["enc"]))])
+
+
+# ---- dishonest provers ---------------------------------------------------------------------------------------------------------
+# a fixed point outside every statement: nobody knows its discrete logarithm to a generator, a key or a commitment
+SHIFT_POINT = R.from_uniform_bytes(hashlib.sha512(b"aeonflux-amd tests: the point dishonest commitments are shifted by").digest())
+
+
+class ShiftingProver(zkp.Prover):
+    """zkp's prover with dishonest commitments: proof number `call` of a show (0 the main proof, 1 + e proof of encryption e) sends
+    R_j + shifts[(call, j)] * SHIFT_POINT, hashes the commitments as sent and answers honestly for that challenge.  Constraint j of
+    that proof is then false by exactly shifts[(call, j)] * SHIFT_POINT (an integer mod l; 0 or absent: honest)."""
+    shifts, calls = {}, 0
+
+    def prove_compact(self, external_random32):
+        cls = ShiftingProver
+        call = cls.calls
+        cls.calls += 1
+        rb = self.t.build_rng()
+        for s in self.scalars:
+            rb.rekey_with_witness_bytes(b"", R.sc_bytes(s))
+        rng = rb.finalize(external_random32)
+        blindings = [R.sc_from_wide(rng.fill_bytes(64)) for _ in self.scalars]
+        coms = []
+        for j, (lhs, terms) in enumerate(self.constraints):
+            c = R.msm([blindings[s] for s, _ in terms], [self.points[p] for _, p in terms])
+            e = cls.shifts.get((call, j), 0) % R.L
+            if e:
+                c = R.add(c, R.mul(e, SHIFT_POINT))
+            enc = R.encode(c)
+            zkp._append_point(self.t, b"blindcom", self.labels[lhs], enc)
+            coms.append(enc)
+        ch = zkp._challenge(self.t)
+        return ch, [(s * ch + b) % R.L for s, b in zip(self.scalars, blindings)], coms
+
+
+def show_shifted(params, ip, skinds, cred, keypair, z_wide, seed, enc_seeds, shifts, strict=False):
+    """pyref as prover of ONE credential (tests.helpers.make_credentials) under `shifts`: (oracle.Presentation, dict(main, enc))"""
+    import oracle
+    saved = S.Prover
+    S.Prover = ShiftingProver
+    ShiftingProver.shifts, ShiftingProver.calls = dict(shifts), 0
+    try:
+        st, q = S.show(params, ip, skinds, cred["values"], cred["t"], cred["U"], cred["V"], keypair, z_wide, seed, enc_seeds, strict=strict)
+    finally:
+        S.Prover = saved
+        ShiftingProver.shifts, ShiftingProver.calls = {}, 0
+    assert st == 0
+    p = oracle.Presentation()
+    p.n_attributes, p.n_responses, p.n_hidden_scalars, p.n_enc_proofs = len(q["kinds"]), len(q["responses"]), len(q["hidden_scalar_indices"]), len(q["enc"])
+
+    def put(dst, b):
+        for k in range(32):
+            dst[k] = b[k]
+    put(p.challenge, q["challenge"]); put(p.C_x_0, q["C_x_0"]); put(p.C_x_1, q["C_x_1"]); put(p.C_V, q["C_V"])
+    for k, r in enumerate(q["responses"]):
+        put(p.responses[k], r)
+    for k in range(p.n_attributes):
+        put(p.C_y[k], q["C_y"][k]); put(p.attr_values[k], q["attr_values"][k]); p.kinds[k] = q["kinds"][k]
+    for k, h in enumerate(q["hidden_scalar_indices"]):
+        p.hidden_scalar_indices[k] = h
+    for k, en in enumerate(q["enc"]):
+        put(p.enc[k].challenge, en["challenge"])
+        for r in range(6):
+            put(p.enc[k].responses[r], en["responses"][r])
+        for f in ("pk", "E1", "E2", "C_y_1", "C_y_2", "C_y_3", "C_y_2p"):
+            put(getattr(p.enc[k], f), en[f])
+        p.enc[k].index = en["index"]
+    return p, dict(main=list(q["commitments"]), enc=[list(en["commitments"]) for en in q["enc"]])
+
+
+def constraint_of(w, n_main):
+    """weight index w of the header's order -> (proof number, constraint within it): the main proof's n_main, then five per proof of
+    encryption"""
+    return (0, w) if w < n_main else (1 + (w - n_main) // 5, (w - n_main) % 5)
+
+
+def cancelling_shifts(rho, a, b, n_main):
+    """the shifts of a forgery against the weights rho of ONE item: constraint a off by rho_b * D, constraint b by -rho_a * D.  Both
+    are false (for nonzero weights), and rho_a * rho_b - rho_b * rho_a = 0 (mod l): the sum under exactly rho is the identity."""
+    assert a != b and rho[a] % R.L and rho[b] % R.L
+    return {constraint_of(a, n_main): rho[b] % R.L, constraint_of(b, n_main): (R.L - rho[a]) % R.L}
+
+
+def forge(d, x, i, shifts, strict=False):
+    """item i of d (tests.helpers.make_credentials) with the prover inputs x (keypairs, z_wide, seeds, enc_seeds, skinds per item) shown
+    by pyref under `shifts` ({}: an honest item)"""
+    return show_shifted(d["params"], d["ip"], x["skinds"], d["creds"][i], x["keypairs"][i], x["z_wide"][i], x["seeds"][i], x["enc_seeds"][i], shifts, strict=strict)

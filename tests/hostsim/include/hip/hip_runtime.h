@@ -9,3 +9,5 @@
 #define __host__
 #define __forceinline__ inline
 #define __restrict__
+// the 16-byte vector load of a weight (batchable.cuh coef_item); on the host nothing more than its four words
+struct uint4 { uint32_t x, y, z, w; };

@@ -160,73 +160,15 @@ def test_damaged_items_get_the_yardsticks_verdicts(n, layout, hide, count, seed)
     assert got == want, [(i, classes[i], g, w) for i, (g, w) in enumerate(zip(got, want)) if g != w]
 
 
-class _ShiftingProver(B.zkp.Prover):
-    """zkp's prover with dishonest commitments: proof number `call` of a show sends R_j + sign * D for the (call, j) in `shifts`,
-    hashes them as sent and answers honestly.  Each constraint is then off by +-D; the errors cancel in any UNWEIGHTED sum."""
-    shifts, calls = {}, 0
-
-    def prove_compact(self, external_random32):
-        R = B.R
-        cls = type(self)
-        call = cls.calls
-        cls.calls += 1
-        rb = self.t.build_rng()
-        for s in self.scalars:
-            rb.rekey_with_witness_bytes(b"", R.sc_bytes(s))
-        rng = rb.finalize(external_random32)
-        blindings = [R.sc_from_wide(rng.fill_bytes(64)) for _ in self.scalars]
-        D = R.mul(777, self.points[0])
-        coms = []
-        for j, (lhs, terms) in enumerate(self.constraints):
-            c = R.msm([blindings[s] for s, _ in terms], [self.points[p] for _, p in terms])
-            sign = cls.shifts.get((call, j), 0)
-            if sign:
-                c = R.add(c, D) if sign > 0 else R.sub(c, D)
-            enc = R.encode(c)
-            B.zkp._append_point(self.t, b"blindcom", self.labels[lhs], enc)
-            coms.append(enc)
-        ch = B.zkp._challenge(self.t)
-        return ch, [(s * ch + b) % R.L for s, b in zip(self.scalars, blindings)], coms
-
-
-def _pyref_show_all(d, hide, count, shifts):
-    """pyref as prover over d's credentials; returns (oracle.Presentation list, commitments list)"""
-    import oracle
-    S = B.S
+def _pyref_show_all(d, hide, count, shifts, strict=False):
+    """pyref as prover over d's credentials, every item under the same `shifts` (tests/batchable_ref.py ShiftingProver: proof `call`,
+    constraint j sends R_j + shifts[(call, j)] * D); returns (oracle.Presentation list, commitments list)"""
     _, _, x = _show_inputs(d, hide, count)
     pres, cms = [], []
-    saved = S.Prover
-    S.Prover = _ShiftingProver
-    try:
-        for c, kp, z, s, e in zip(d["creds"], x["keypairs"], x["z_wide"], x["seeds"], x["enc_seeds"]):
-            _ShiftingProver.shifts, _ShiftingProver.calls = shifts, 0
-            st, q = S.show(d["params"], d["ip"], x["skinds"], c["values"], c["t"], c["U"], c["V"], kp, z, s, e)
-            assert st == 0
-            p = oracle.Presentation()
-            p.n_attributes, p.n_responses, p.n_hidden_scalars, p.n_enc_proofs = len(q["kinds"]), len(q["responses"]), len(q["hidden_scalar_indices"]), len(q["enc"])
-
-            def put(dst, b):
-                for k in range(32):
-                    dst[k] = b[k]
-            put(p.challenge, q["challenge"]); put(p.C_x_0, q["C_x_0"]); put(p.C_x_1, q["C_x_1"]); put(p.C_V, q["C_V"])
-            for k, r in enumerate(q["responses"]):
-                put(p.responses[k], r)
-            for k in range(p.n_attributes):
-                put(p.C_y[k], q["C_y"][k]); put(p.attr_values[k], q["attr_values"][k]); p.kinds[k] = q["kinds"][k]
-            for k, h in enumerate(q["hidden_scalar_indices"]):
-                p.hidden_scalar_indices[k] = h
-            for k, en in enumerate(q["enc"]):
-                put(p.enc[k].challenge, en["challenge"])
-                for r in range(6):
-                    put(p.enc[k].responses[r], en["responses"][r])
-                for f in ("pk", "E1", "E2", "C_y_1", "C_y_2", "C_y_3", "C_y_2p"):
-                    put(getattr(p.enc[k], f), en[f])
-                p.enc[k].index = en["index"]
-            pres.append(p)
-            cms.append(dict(main=list(q["commitments"]), enc=[list(en["commitments"]) for en in q["enc"]]))
-    finally:
-        S.Prover = saved
-        _ShiftingProver.shifts = {}
+    for c, kp, z, s, e in zip(d["creds"], x["keypairs"], x["z_wide"], x["seeds"], x["enc_seeds"]):
+        p, cm = B.show_shifted(d["params"], d["ip"], x["skinds"], c, kp, z, s, e, shifts, strict=strict)
+        pres.append(p)
+        cms.append(cm)
     return pres, cms
 
 
@@ -307,13 +249,7 @@ def test_every_plan_variant_mode_and_schedule_gives_the_yardsticks_statuses_and_
 
 def _strict_items(d, hide, count):
     """honest strict-mode items: pyref's strict show (the oracle's show restated with the strict statement)"""
-    S = B.S
-    saved = S.show
-    try:
-        S.show = lambda *a, **k: saved(*a, **dict(k, strict=True))
-        return _pyref_show_all(d, hide, count, {})
-    finally:
-        S.show = saved
+    return _pyref_show_all(d, hide, count, {}, strict=True)
 
 
 def test_edge_scalars_in_the_responses_and_weights_at_both_ends():

@@ -34,6 +34,8 @@ import aeonflux_amd as afx
 afx.LIB_PATH = %(lib)r
 from aeonflux_amd import batch, wire
 from tests.helpers import make_credentials
+from tests.batchable_ref import LARGEST_COEF_JOB_16_STRICT
+longest = {}
 rb = lambda *s: np.zeros(s, np.uint8)
 for strict in (0, 1):
     for n, layout, hide in ((4, "SSPE", [0, 3]), (16, "SSSSSSSSPPPPEEEE", [12, 13, 14, 15]), (8, "SSPPEEEE", [4, 5, 6, 7]), (1, "S", []), (3, "ESS", [0])):
@@ -65,6 +67,7 @@ for strict in (0, 1):
             batch.verify_presentations_batchable(ctx, shape, pres, cm, bytes(32))
             ctx.set_plan_variants(0)
         ctx.set_small_batch_items(4096)
+        longest[(strict, layout)] = C.CDLL(afx.LIB_PATH).fake_coef_most_triples(1)     # the longest coefficient job of these plans
         # no challenge arrays at all
         nochal = dict(pres, challenge=None, enc=[dict(e, challenge=None) for e in pres["enc"]])
         batch.verify_presentations_batchable(ctx, shape, nochal, cm, bytes(32))
@@ -128,6 +131,10 @@ for strict in (0, 1):
         assert L.afx_batchable_main_commitments(ctx.h, C.byref(bad)) == 0
         assert batch.verify_presentations_batchable(ctx, bad, pres, cm, bytes(32)).tolist() == [1, 1, 1]
         ctx.close()
+
+# the job length tests/test_batchable_coef_on_host.py runs the kernel's arithmetic at is the plan's
+assert longest[(1, "SSSSSSSSPPPPEEEE")] == LARGEST_COEF_JOB_16_STRICT == max(longest.values()), longest
+print("longest coefficient jobs", longest)
 
 # operation counts of the C3 shape in the plan of large passes: derived bounds, not measurements
 d = make_credentials(8, "SSPPEEEE", 3, b"hostsim-batchable-counts")
