@@ -178,6 +178,13 @@ def lib():
         _LIB.afx_keypairs_derive.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB.afx_encrypt.argtypes = [C.c_void_p, C.POINTER(KeypairsSoA), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB.afx_decrypt.argtypes = [C.c_void_p, C.POINTER(KeypairsSoA), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        # (plaintexts, keypairs, encryption and decryption over device rows, and SHA-512 as a batch primitive)
+        if hasattr(_LIB, "afx_sha512"):
+            _LIB.afx_sha512.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+            _LIB.afx_plaintexts_from_bytes_dev.argtypes = _LIB.afx_plaintexts_from_bytes.argtypes + [C.c_void_p]
+            _LIB.afx_keypairs_derive_dev.argtypes = _LIB.afx_keypairs_derive.argtypes
+            _LIB.afx_encrypt_dev.argtypes = _LIB.afx_encrypt.argtypes
+            _LIB.afx_decrypt_dev.argtypes = _LIB.afx_decrypt.argtypes
         _LIB.afx_wire_header_bytes.restype = C.c_size_t
         _LIB.afx_wire_header_bytes.argtypes = [C.POINTER(Shape)]
         _LIB.afx_wire_cells_per_record.restype = C.c_uint32

@@ -325,6 +325,95 @@ def scalars_from_wide(ctx, wide):
     return out
 
 
+def sha512(ctx, msgs):
+    """SHA-512 of every row of msgs [count, msg_len] (msg_len 0 .. 1024) on the device (afx_sha512) -> [count, 64]"""
+    msgs = _u8(msgs)
+    out = np.zeros((msgs.shape[0], 64), np.uint8)
+    check(lib().afx_sha512(ctx.h, msgs.ctypes.data, msgs.shape[1], msgs.shape[0], out.ctypes.data))
+    return out
+
+
+def plaintexts_from_bytes(ctx, msgs):
+    """Plaintext::from(&[u8; 30]) over msgs [count, 30] (afx_plaintexts_from_bytes) -> M1, M2, m3 ([count, 32]), counters [count]"""
+    msgs = _u8(msgs)
+    cnt = msgs.shape[0]
+    assert msgs.shape == (cnt, 30)
+    M1, M2, m3 = (np.zeros((cnt, 32), np.uint8) for _ in range(3))
+    counters = np.zeros(cnt, np.uint32)
+    check(lib().afx_plaintexts_from_bytes(ctx.h, msgs.ctypes.data, cnt, M1.ctypes.data, M2.ctypes.data, m3.ctypes.data, counters.ctypes.data))
+    return M1, M2, m3, counters
+
+
+def keypairs_derive(ctx, master_secrets):
+    """Keypair::derive over master_secrets [count, 64] (afx_keypairs_derive) -> dict(a, a0, a1, pk), [count, 32] each"""
+    ms = _u8(master_secrets)
+    cnt = ms.shape[0]
+    assert ms.shape == (cnt, 64)
+    kp = {f: np.zeros((cnt, 32), np.uint8) for f in ("a", "a0", "a1", "pk")}
+    check(lib().afx_keypairs_derive(ctx.h, ms.ctypes.data, cnt, *(kp[f].ctypes.data for f in ("a", "a0", "a1", "pk"))))
+    return kp
+
+
+def _keypairs_soa(kp, ptr):
+    return KeypairsSoA(*(ptr(kp[f]) if kp.get(f) is not None else None for f in ("a", "a0", "a1", "pk")))
+
+
+def encrypt(ctx, keypairs, M1, M2, m3):
+    """Keypair::encrypt over arrays (afx_encrypt): keypairs = dict(a, a0, a1[, pk]) -> E1, E2 ([count, 32]), status [count]"""
+    kp = {f: _u8(v) for f, v in keypairs.items() if v is not None}
+    M1, M2, m3 = _u8(M1), _u8(M2), _u8(m3)
+    cnt = M1.shape[0]
+    E1, E2 = np.zeros((cnt, 32), np.uint8), np.zeros((cnt, 32), np.uint8)
+    status = np.full(cnt, 255, np.uint8)
+    soa = _keypairs_soa(kp, lambda a: a.ctypes.data)
+    check(lib().afx_encrypt(ctx.h, C.byref(soa), M1.ctypes.data, M2.ctypes.data, m3.ctypes.data, cnt, E1.ctypes.data, E2.ctypes.data, status.ctypes.data))
+    return E1, E2, status
+
+
+def decrypt(ctx, keypairs, E1, E2, messages=True):
+    """Keypair::decrypt over arrays (afx_decrypt) -> M1, M2, m3 ([count, 32]), messages ([count, 30], or None), status [count]"""
+    kp = {f: _u8(v) for f, v in keypairs.items() if v is not None}
+    E1, E2 = _u8(E1), _u8(E2)
+    cnt = E1.shape[0]
+    M1, M2, m3 = (np.zeros((cnt, 32), np.uint8) for _ in range(3))
+    msg = np.zeros((cnt, 30), np.uint8) if messages else None
+    status = np.full(cnt, 255, np.uint8)
+    soa = _keypairs_soa(kp, lambda a: a.ctypes.data)
+    check(lib().afx_decrypt(ctx.h, C.byref(soa), E1.ctypes.data, E2.ctypes.data, cnt, M1.ctypes.data, M2.ctypes.data, m3.ctypes.data,
+                            msg.ctypes.data if messages else None, status.ctypes.data))
+    return M1, M2, m3, msg, status
+
+
+# The *_dev forms: every array is a device pointer - an int, or anything that carries one as .data_ptr() (a torch tensor) or .ptr -
+# to rows the caller allocated on the context's device; the call is asynchronous on afx_ctx_stream (ctx.synchronize() waits for it).
+def _dptr(x):
+    if x is None or isinstance(x, int):
+        return x
+    return x.data_ptr() if hasattr(x, "data_ptr") else x.ptr
+
+
+def plaintexts_from_bytes_dev(ctx, msgs, count, M1, M2, m3, counters, status):
+    """afx_plaintexts_from_bytes_dev: msgs [count][30] -> M1, M2, m3 ([count][32]), counters ([count] u32, or None), status [count]"""
+    check(lib().afx_plaintexts_from_bytes_dev(ctx.h, _dptr(msgs), count, _dptr(M1), _dptr(M2), _dptr(m3), _dptr(counters), _dptr(status)))
+
+
+def keypairs_derive_dev(ctx, master_secrets, count, a, a0, a1, pk):
+    """afx_keypairs_derive_dev: master_secrets [count][64] -> a, a0, a1, pk ([count][32] each)"""
+    check(lib().afx_keypairs_derive_dev(ctx.h, _dptr(master_secrets), count, _dptr(a), _dptr(a0), _dptr(a1), _dptr(pk)))
+
+
+def encrypt_dev(ctx, keypairs, M1, M2, m3, count, E1, E2, status):
+    """afx_encrypt_dev: keypairs = dict(a, a0, a1[, pk]) of device rows"""
+    soa = _keypairs_soa(keypairs, _dptr)
+    check(lib().afx_encrypt_dev(ctx.h, C.byref(soa), _dptr(M1), _dptr(M2), _dptr(m3), count, _dptr(E1), _dptr(E2), _dptr(status)))
+
+
+def decrypt_dev(ctx, keypairs, E1, E2, count, M1, M2, m3, messages, status):
+    """afx_decrypt_dev: messages ([count][30]) may be None"""
+    soa = _keypairs_soa(keypairs, _dptr)
+    check(lib().afx_decrypt_dev(ctx.h, C.byref(soa), _dptr(E1), _dptr(E2), count, _dptr(M1), _dptr(M2), _dptr(m3), _dptr(messages), _dptr(status)))
+
+
 def multiscalar_mul(ctx, scalars, points):
     """out[i] = sum_k scalars[k,i] * points[k,i];  scalars, points: [n_terms, count, 32]"""
     scalars, points = _u8(scalars), _u8(points)

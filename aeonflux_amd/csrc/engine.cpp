@@ -12,6 +12,9 @@
 // (a weak reference, like afxk_draw in plans.cpp: the host simulation builds of the engine link the launchers they need from
 // tests/hostsim, and only the batchable simulation brings this one)
 hipError_t afxk_coef(hipStream_t s, const afx_coef_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
+// (likewise: only the plaintext simulation, tests/hostsim/fake_plaintext.cpp, brings these two)
+hipError_t afxk_sha512_jobs(hipStream_t s, const afx_sha512_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
+hipError_t afxk_encode_to_group(hipStream_t s, const afx_encode_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
 
 namespace afx {
 namespace { size_t job_size(LaunchKind k); }   // bytes of one job of a launch kind (below, with the relocation)
@@ -965,6 +968,29 @@ void Assembler::reduce_wide(const uint8_t* wide, uint8_t* out) {
   const afx_reduce_job j = { wide, out };
   add_jobs(L_REDUCE_WIDE, std::vector<afx_reduce_job>(1, j));
 }
+void Assembler::sha512(const afx_sha512_job& job) {
+  flush_maps();
+  flush_encodings();   // (the range hashed may be an encoding a small pass still has queued: decrypt's M1')
+  afx_sha512_job j;
+  memset(&j, 0, sizeof j);
+  j.src = job.src; j.out = job.out; j.copy = job.copy; j.stride = job.stride; j.offset = job.offset; j.len = job.len;
+  add_jobs(L_SHA512, std::vector<afx_sha512_job>(1, j));
+}
+void Assembler::encode_to_group(const afx_encode_job& job) {
+  flush_maps();
+  flush_encodings();   // (a failing item zeroes rows that queued encodings write: they go first)
+  stats.decodings += 4;   // the mean number of candidates tried
+  stats.field_mul += 4 * AFX_DECODE_MUL; stats.field_sq += 4 * AFX_DECODE_SQ;
+  stats.chain_mul += 4 * AFX_CHAIN_SQRT_MUL; stats.chain_sq += 4 * AFX_CHAIN_SQRT_SQ;
+  add_jobs(L_ENCODE, std::vector<afx_encode_job>(1, job));
+}
+// rows of `count` dwords each: the opening launch's kernel (k_fill_u32) covers that many per grid row
+void Assembler::wipe(void* p, size_t bytes_per_item) {
+  flush_maps();
+  std::vector<afx_fill_job> jobs;
+  for (size_t k = 0; k < bytes_per_item / 4; k++) { const afx_fill_job f = { (uint32_t*)p + k * (size_t)count, 0u, count }; jobs.push_back(f); }
+  add_jobs(L_FILL_BAD, jobs);
+}
 void Assembler::copy(uint8_t* dst, const uint8_t* src, size_t bytes) {
   Launch l; l.kind = L_COPY; l.in = src; l.out = dst; l.bytes = bytes;
   launches.push_back(l);
@@ -1046,6 +1072,8 @@ size_t job_size(LaunchKind k) {
     case L_TABLE_AFFINE: return sizeof(afx_table_job);
     case L_POWERS: return sizeof(afx_powers_job);
     case L_COEF: return sizeof(afx_coef_job);
+    case L_SHA512: return sizeof(afx_sha512_job);
+    case L_ENCODE: return sizeof(afx_encode_job);
     default: return 0;
   }
 }
@@ -1110,6 +1138,8 @@ void Plan::relocate(uint8_t* nblob, uint8_t* nws, uint8_t* nin, uint8_t* nout) {
         for (uint32_t i = 0; i < l.njobs; i++) { afx_powers_job& j = ((afx_powers_job*)J)[i]; m.fix(j.src); for (uint32_t k = 0; k < AFX_POWERS_MAX; k++) m.fix(j.out[k]); }
         break;
       case L_COEF: for (uint32_t i = 0; i < l.njobs; i++) { afx_coef_job& j = ((afx_coef_job*)J)[i]; m.fix(j.weights); m.fix(j.triples); m.fix(j.operands); m.fix(j.out); } break;
+      case L_SHA512: for (uint32_t i = 0; i < l.njobs; i++) { afx_sha512_job& j = ((afx_sha512_job*)J)[i]; m.fix(j.src); m.fix(j.out); m.fix(j.copy); } break;
+      case L_ENCODE: for (uint32_t i = 0; i < l.njobs; i++) { afx_encode_job& j = ((afx_encode_job*)J)[i]; m.fix(j.msgs); m.fix(j.M1); m.fix(j.counters); m.fix(j.zero_a); m.fix(j.zero_b); } break;
       case L_COPY: m.fix(l.in); m.fix(l.out); break;
       case L_KINDS: break;
     }
@@ -1324,6 +1354,14 @@ int run_plans(afx_ctx* ctx, int lane, Plan* const* plans, size_t n) {
       case L_COEF:
         if (!afxk_coef) { set_error("batchable verification: no k_coef launcher in this build"); return AFX_E_NO_DEVICE; }
         AFX_HIP(afxk_coef(s, (const afx_coef_job*)jobs, nrows, rw, passes, max_count));
+        break;
+      case L_SHA512:
+        if (!afxk_sha512_jobs) { set_error("no k_sha512 launcher in this build"); return AFX_E_NO_DEVICE; }
+        AFX_HIP(afxk_sha512_jobs(s, (const afx_sha512_job*)jobs, nrows, rw, passes, max_count));
+        break;
+      case L_ENCODE:
+        if (!afxk_encode_to_group) { set_error("no k_encode_to_group launcher in this build"); return AFX_E_NO_DEVICE; }
+        AFX_HIP(afxk_encode_to_group(s, (const afx_encode_job*)jobs, nrows, rw, passes, max_count));
         break;
       case L_MSM_TABLES: AFX_HIP(afxk_msm_tables(s, odd, (const afx_table_job*)jobs, nrows, rw, passes, max_count)); break;
       case L_MSM_FIXED: case L_MSM_WINDOW: case L_MSM_NAF: {

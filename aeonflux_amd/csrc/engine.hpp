@@ -267,7 +267,7 @@ namespace afx {
 
 // L_MSM_WINDOW keeps the slot the single k_msm kernel had (timing names: statements.cpp KIND_NAMES)
 enum LaunchKind { L_FILL_BAD, L_DECODE, L_SCCHECK, L_POINTOP, L_SCALAROP, L_MSM_WINDOW, L_HASH, L_FROM_UNIFORM, L_REDUCE_WIDE, L_COPY, L_FINISH,
-                  L_MSM_FIXED, L_MSM_NAF, L_MSM_TABLES, L_COMPRESS, L_POINTSUM, L_NEGENC, L_TABLE_AFFINE, L_POWERS, L_COEF, L_KINDS };
+                  L_MSM_FIXED, L_MSM_NAF, L_MSM_TABLES, L_COMPRESS, L_POINTSUM, L_NEGENC, L_TABLE_AFFINE, L_POWERS, L_COEF, L_SHA512, L_ENCODE, L_KINDS };
 // the kernels whose grid rows WALK a range of the launch's jobs (afx_walk_row) instead of taking one job each (afx_row)
 inline bool walks(LaunchKind k) { return k == L_COMPRESS || k == L_NEGENC || k == L_TABLE_AFFINE; }
 
@@ -357,6 +357,9 @@ class Assembler {
   void hash(const std::vector<afx_hash_program>& progs);
   void from_uniform(const uint8_t* wide, uint8_t* out_enc, int32_t* out_var);
   void reduce_wide(const uint8_t* wide, uint8_t* out);
+  void sha512(const afx_sha512_job& job);             // out = SHA-512 of a byte range of every item's row (plan.h afx_sha512_job)
+  void encode_to_group(const afx_encode_job& job);    // M1 = encode_to_group(msgs) (plan.h afx_encode_job); runs behind everything queued
+  void wipe(void* p, size_t bytes_per_item);          // zeroes a [count][bytes_per_item] array of the pass in stream order (a multiple of 4 bytes)
   void copy(uint8_t* dst, const uint8_t* src, size_t bytes);   // device-to-device
   void finish(uint8_t* status_dev, uint8_t fail_code);
 

@@ -59,3 +59,9 @@ hipError_t afxk_draw(hipStream_t s, const afx_draw_job* jobs, uint32_t njobs, ui
 hipError_t afxk_batch_weights(hipStream_t s, const uint8_t* seed, uint64_t index0, uint32_t label, uint32_t n_weights, uint32_t count, uint8_t* weights);
 // one coefficient of the weighted sum per job (plan.h afx_coef_job)
 hipError_t afxk_coef(hipStream_t s, const afx_coef_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count);
+// SHA-512 of a byte range of every item's row and encode_to_group's counter search (plan.h afx_sha512_job, afx_encode_job;
+// sha512.cuh).  The host sources refer to these three through weak declarations: a host simulation links them only if it hashes.
+hipError_t afxk_sha512_jobs(hipStream_t s, const afx_sha512_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count);
+hipError_t afxk_encode_to_group(hipStream_t s, const afx_encode_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count);
+// direct form (afx_sha512): out[i] = SHA-512(src + i * stride + offset, len), out [count][64]
+hipError_t afxk_sha512(hipStream_t s, const uint8_t* src, uint32_t stride, uint32_t offset, uint32_t len, uint8_t* out, uint32_t count);

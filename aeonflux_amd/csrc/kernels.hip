@@ -17,11 +17,14 @@
 //                       schedule; squeezes challenges / blinding factors                   (P2, P4 iv-v)
 //   k_finish            per-item status byte
 //   k_from_uniform, k_reduce_wide   RistrettoPoint::from_uniform_bytes, Scalar::from_bytes_mod_order_wide
+//   k_sha512            SHA-512 of a byte range of every item's row (sha512.cuh): what turns application data into attributes
+//   k_encode_to_group   encoding.rs encode_to_group: the first counter whose candidate decodes
 #include <hip/hip_runtime.h>
 #include "ge.cuh"
 #include "keccak.cuh"
 #include "plan.h"
 #include "sc.cuh"
+#include "sha512.cuh"
 
 // ---------------------------------------------------------------------------------------------
 // memory helpers
@@ -1824,6 +1827,92 @@ __global__ void __launch_bounds__(AFX_BLOCK) k_draw(const afx_draw_job* __restri
   }
 }
 
+// SHA-512 of one byte range per item (plan.h afx_sha512_job), a lane each: state and schedule in registers (sha512.cuh), no LDS, no
+// scratch.  The range's place and length are the launch's, so every branch on them is uniform; whole dwords are read where the
+// caller's layout puts every item's range on a 4-byte boundary (64- and 32-byte rows), single bytes otherwise (30-byte rows, a
+// range that starts at byte 1 of an encoding).
+AFX_DEV void sha512_item(const afx_sha512_job& job, uint32_t item) {
+  const uint8_t* m = job.src + (uint64_t)item * job.stride + job.offset;
+  uint64_t h[8];
+  const bool aligned = ((reinterpret_cast<uintptr_t>(job.src) | job.stride | job.offset) & 3u) == 0;   // (uniform)
+  if (aligned) sha512_words<true>(h, m, job.len);
+  else sha512_words<false>(h, m, job.len);
+  uint32_t d[16];
+  sha512_digest_dwords(d, h);
+  uint4* out = reinterpret_cast<uint4*>(job.out + 64ull * item);
+#pragma unroll
+  for (int i = 0; i < 4; i++) out[i] = make_uint4(d[4 * i], d[4 * i + 1], d[4 * i + 2], d[4 * i + 3]);
+  if (job.copy) {   // the bytes hashed, packed (decrypt's `messages`)
+    uint8_t* c = job.copy + (uint64_t)item * job.len;
+    for (uint32_t k = 0; k < job.len; k++) c[k] = m[k];
+  }
+}
+__global__ void __launch_bounds__(AFX_BLOCK) k_sha512(const afx_sha512_job* __restrict__ jobs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
+  const afx_sha512_job job = *row_job(jobs, rows);
+  const afx_pass pass = passes[row_pass_index(rows)];
+  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
+  if (item >= pass.count) return;
+  sha512_item(job, item);
+}
+// the direct form (afx_sha512): the job as a kernel argument
+__global__ void __launch_bounds__(AFX_BLOCK) k_sha512_direct(const afx_sha512_job job, uint32_t count) {
+  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
+  if (item >= count) return;
+  sha512_item(job, item);
+}
+
+// the 30 message bytes as dwords (byte k of the message is byte k of mw; bytes 30 and 31 are zero): single-byte loads, a row of 30
+// bytes promises no alignment
+AFX_DEV void load_msg30(uint32_t mw[8], const uint8_t* m) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    mw[i] = 0;
+#pragma unroll
+    for (int b = 0; b < 4; b++)
+      if (4 * i + b < 30) mw[i] |= (uint32_t)m[4 * i + b] << (8 * b);
+  }
+}
+// encode_to_group (the reference's src/encoding.rs:56-70), a lane per 30-byte message: the counters 0 .. 8191 in the reference's
+// order (`i` fastest: sha512.cuh encode_candidate) until a candidate decodes - the validity test k_decode and k_validate run.
+// THE TRIP COUNT DEPENDS ON THE MESSAGE, exactly as the reference's loop does (a candidate decodes with probability 1/4: four
+// tries on average, and a wave waits for its slowest lane).  No counter below 8192 decodes (the reference panics): the item fails,
+// M1, its counter and the rows of the job's other outputs are zeroed.
+__global__ void __launch_bounds__(AFX_BLOCK, 2) k_encode_to_group(const afx_encode_job* __restrict__ jobs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
+  const afx_encode_job job = *row_job(jobs, rows);
+  const afx_pass pass = passes[row_pass_index(rows)];
+  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
+  if (item >= pass.count) return;
+  const uint8_t* m = job.msgs + 30ull * item;
+  uint32_t ctr = 0;
+  bool found = false;
+  // (the message is read again for every candidate - 30 cached bytes against a square-root chain - and the winning candidate is
+  // written out again after the loop: kept in registers across the decoding, the two would push the kernel past k_decode's
+  // registers and into scratch)
+#pragma unroll 1
+  for (; ctr < 128u * 64u; ctr++) {
+    uint32_t mw[8], w[8];
+    load_msg30(mw, m);
+    encode_candidate(w, mw, ctr);
+    ge_p3 P;
+    if (ristretto_decode(P, w)) { found = true; break; }
+  }
+  uint32_t w[8];
+  if (found) {
+    uint32_t mw[8];
+    load_msg30(mw, m);
+    encode_candidate(w, mw, ctr);
+  } else {
+    ctr = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) w[i] = 0;
+    atomicOr(&pass.bad[item], AFX_BAD_DECODE);
+    if (job.zero_a) enc_store(job.zero_a, item, w);
+    if (job.zero_b) enc_store(job.zero_b, item, w);
+  }
+  enc_store(job.M1, item, w);
+  if (job.counters) job.counters[item] = ctr;
+}
+
 // ---------------------------------------------------------------------------------------------
 // host-callable launch wrappers (engine.cpp is plain C++ and never sees a kernel symbol)
 // ---------------------------------------------------------------------------------------------
@@ -2033,6 +2122,20 @@ hipError_t afxk_soa_to_aos(hipStream_t s, const uint8_t* soa, uint8_t* rec, cons
 hipError_t afxk_draw(hipStream_t s, const afx_draw_job* jobs, uint32_t njobs, uint32_t max_count) {
   if (!njobs || !max_count) return hipSuccess;
   hipLaunchKernelGGL(k_draw, dim3((max_count + AFX_BLOCK - 1) / AFX_BLOCK, njobs), dim3(AFX_BLOCK), 0, s, jobs, (const afx_row*)nullptr);
+  return hipGetLastError();
+}
+hipError_t afxk_sha512_jobs(hipStream_t s, const afx_sha512_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) {
+  hipLaunchKernelGGL(k_sha512, grid_for(max_count, njobs), dim3(block_for(max_count)), 0, s, jobs, rows, passes);
+  return hipGetLastError();
+}
+hipError_t afxk_sha512(hipStream_t s, const uint8_t* src, uint32_t stride, uint32_t offset, uint32_t len, uint8_t* out, uint32_t count) {
+  if (!count) return hipSuccess;
+  const afx_sha512_job job = { src, out, nullptr, stride, offset, len, 0 };
+  hipLaunchKernelGGL(k_sha512_direct, dim3((count + AFX_BLOCK - 1) / AFX_BLOCK), dim3(AFX_BLOCK), 0, s, job, count);
+  return hipGetLastError();
+}
+hipError_t afxk_encode_to_group(hipStream_t s, const afx_encode_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) {
+  hipLaunchKernelGGL(k_encode_to_group, grid_for(max_count, njobs), dim3(block_for(max_count)), 0, s, jobs, rows, passes);
   return hipGetLastError();
 }
 

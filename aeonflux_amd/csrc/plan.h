@@ -113,6 +113,13 @@ typedef struct { uint32_t* p; uint32_t v, n; } afx_fill_job;                    
 typedef struct { const uint32_t* bad; uint8_t* status; uint32_t count, fail_code; } afx_finish_job;     /* status[i] = bad[i] ? code : 0 */
 typedef struct { const uint8_t* wide; uint8_t* out_enc; int32_t* out_var; } afx_uniform_job;            /* RistrettoPoint::from_uniform_bytes */
 typedef struct { const uint8_t* wide; uint8_t* out; } afx_reduce_job;                                   /* Scalar::from_bytes_mod_order_wide  */
+/* k_sha512, one lane per item: out[item] = SHA-512 of the `len` bytes at src + item * stride + offset, 64 bytes (16-byte aligned rows).
+ * `copy` (or null): the bytes hashed go there too, packed, [count][len] - the messages a decryption recovers. */
+typedef struct { const uint8_t* src; uint8_t* out; uint8_t* copy; uint32_t stride, offset, len, pad; } afx_sha512_job;
+/* k_encode_to_group, one lane per item: M1[item] = the first candidate of msgs[item] ([count][30]) that decodes, counters[item] (or
+ * null) its counter.  An item none of whose 8192 candidates decodes fails (AFX_BAD_DECODE) and gets zeros in M1, its counter and its
+ * rows of zero_a / zero_b (the call's other [count][32] outputs, or null). */
+typedef struct { const uint8_t* msgs; uint8_t* M1; uint32_t* counters; uint8_t* zero_a; uint8_t* zero_b; } afx_encode_job;
 /* k_draw, one grid row per job: item i of the row gets draw(seed, stream, index + i, label) (keccak.cuh shake256_draw), AFX_DRAW_LEN(label)
  * bytes at dst + i * AFX_DRAW_LEN(label).  `seed`: the call's 40 staged bytes seed || u64le(stream), 8-byte aligned; dst 16-byte aligned. */
 typedef struct { const uint8_t* seed; uint8_t* dst; uint64_t index; uint32_t count, label; } afx_draw_job;

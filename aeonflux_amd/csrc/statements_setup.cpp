@@ -1,11 +1,28 @@
-// Cold-path utilities of the crate, batch form.  SHA-512 runs on the host (byte hashing);
-// every field / group / scalar operation still runs in the HIP kernels.
+// Setup utilities of the crate, batch form, and what turns application data into attributes and back:
+// plaintexts from bytes, derived keypairs, encryption and decryption.  Each of those four is ONE plan over device rows (the *_dev
+// forms; the host-pointer forms stage their rows once, run it and fetch once): SHA-512 (k_sha512), encode_to_group's counter
+// search (k_encode_to_group) and every field / group / scalar operation run in the HIP kernels, hashes of key material and of a
+// recovered plaintext are zeroed on the device before the call completes.
 //   SystemParameters::hash_and_pray   /root/reference/src/parameters.rs:196-326
 //   Plaintext::from(&[u8; 30])        /root/reference/src/symmetric.rs:135-143, encode_to_group src/encoding.rs:56-70
 //   Keypair::derive                   /root/reference/src/symmetric.rs:197-215
 //   Keypair::encrypt / decrypt        /root/reference/src/symmetric.rs:252-261, 273-289 (decode_from_group src/encoding.rs:75-82)
-#include "sha512_host.hpp"
+#include "sha512_host.hpp"   // (only the bodies kept for builds without the hash kernels read it: see have_hash_kernels)
 #include "statements.hpp"
+
+// Weak references, like afxk_coef in engine.cpp: the host simulation of tests/test_hostsim.py links the engine against stand-in
+// launchers that know nothing of these three, and its calls of afx_keypairs_derive, afx_encrypt and afx_decrypt must still succeed.
+hipError_t afxk_sha512_jobs(hipStream_t s, const afx_sha512_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
+hipError_t afxk_encode_to_group(hipStream_t s, const afx_encode_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
+hipError_t afxk_sha512(hipStream_t s, const uint8_t* src, uint32_t stride, uint32_t offset, uint32_t len, uint8_t* out, uint32_t count) __attribute__((weak));
+// false only in a build without kernels.hip's launchers (a host simulation): the three host-pointer calls that hash then take the
+// bodies below that hash on the host (*_without_hash_kernels), which exist for such builds alone - the library never does
+static bool have_hash_kernels() { return afxk_sha512_jobs && afxk_encode_to_group && afxk_sha512; }
+static int need_hash_kernels() {
+  if (have_hash_kernels()) return AFX_OK;
+  set_error("no k_sha512 / k_encode_to_group launcher in this build");
+  return AFX_E_NO_DEVICE;
+}
 
 static afx_scalarop_job mk_sop(const uint8_t* a, uint32_t as_, const uint8_t* b, uint32_t bs, const uint8_t* c, uint32_t cs, uint8_t* out) {
   afx_scalarop_job o;
@@ -114,11 +131,7 @@ extern "C" int afx_system_parameters_generate(int device, uint32_t n, const uint
   return AFX_OK;
 } catch (...) { return afx::exception_rc(); }
 
-extern "C" int afx_plaintexts_from_bytes(afx_ctx* ctx, const uint8_t* msgs, size_t count, uint8_t* M1, uint8_t* M2, uint8_t* m3, uint32_t* counters) try {
-  CtxLock lock__(ctx);
-  if (!ctx || !msgs || !M1 || !M2 || !m3) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  if (count == 0) return AFX_OK;
-  AFX_HIP(hipSetDevice(ctx->device));
+static int plaintexts_without_hash_kernels(afx_ctx* ctx, const uint8_t* msgs, size_t count, uint8_t* M1, uint8_t* M2, uint8_t* m3, uint32_t* counters) {
   int rc;
   // M2 = HashToG(m), m3 = HashToZZq(m): SHA-512 on the host, Elligator / reduction on the GPU
   {
@@ -164,13 +177,9 @@ extern "C" int afx_plaintexts_from_bytes(afx_ctx* ctx, const uint8_t* msgs, size
   }
   if (!pending.empty()) { set_error("encode_to_group found no representative (the reference panics)"); return AFX_E_BAD_ARGS; }
   return AFX_OK;
-} catch (...) { return afx::exception_rc(); }
+}
 
-extern "C" int afx_keypairs_derive(afx_ctx* ctx, const uint8_t* master_secrets, size_t count, uint8_t* a, uint8_t* a0, uint8_t* a1, uint8_t* pk) try {
-  CtxLock lock__(ctx);
-  if (!ctx || !master_secrets || !a || !a0 || !a1 || !pk) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  if (count == 0) return AFX_OK;
-  AFX_HIP(hipSetDevice(ctx->device));
+static int derive_without_hash_kernels(afx_ctx* ctx, const uint8_t* master_secrets, size_t count, uint8_t* a, uint8_t* a0, uint8_t* a1, uint8_t* pk) {
   int rc;
   // a = H(master), a0 = H(a), a1 = H(a0)  (symmetric.rs:202-204)
   std::vector<uint8_t> wide(64 * count);   // SHA-512 outputs that reduce to the secret keys
@@ -200,8 +209,32 @@ extern "C" int afx_keypairs_derive(afx_ctx* ctx, const uint8_t* master_secrets, 
   });
   if (rc) return rc;
   return sync_fetch(ctx, pk, st.dev(o_pk), 32 * count);
-} catch (...) { return afx::exception_rc(); }
+}
 
+// Keypair::encrypt over device rows: E1 = (a0 + a1*m3)*M2, E2 = a*E1 + M1  (symmetric.rs:252-261)
+static int encrypt_on_device(afx_ctx* ctx, const uint8_t* a, const uint8_t* a0, const uint8_t* a1, const uint8_t* M1, const uint8_t* M2, const uint8_t* m3, size_t count,
+                             uint8_t* E1, uint8_t* E2, uint8_t* status) {
+  return run_chunked(ctx, count, [&](Assembler& as, size_t off, uint32_t) {
+    as.secret_scalars = true;   // the user's symmetric key: afx_ctx_set_secret_independent_addressing
+    int32_t *v_M1 = as.new_var(), *v_M2 = as.new_var(), *v_E1 = as.new_var();
+    uint8_t* k = as.new_enc();
+    as.sccheck({ { a + 32 * off }, { a0 + 32 * off }, { a1 + 32 * off }, { m3 + 32 * off } });
+    as.decode({ { M1 + 32 * off, v_M1, 0 }, { M2 + 32 * off, v_M2, 0 } });
+    as.scalarop({ mk_sop(a1 + 32 * off, 32, m3 + 32 * off, 32, a0 + 32 * off, 32, k) });                       // a0 + a1*m3
+    afx_msm_job jE1 = mk_msm({ mk_term(k, 32, v_M2, -1, false) }, nullptr, v_E1, E1 + 32 * off);                // E1 = M2*(a0 + a1*m3)
+    jE1.leave_half = 1;   // an output and the base of E2's term: plan.h afx_msm_job.leave_half
+    as.msm({ jE1 });
+    as.msm({ mk_msm({ mk_term(a + 32 * off, 32, v_E1, -1, false) }, v_M1, nullptr, E2 + 32 * off) });          // E2 = E1*a + M1
+    as.finish(status + off, AFX_ST_VERIFICATION_FAILURE);
+  });
+}
+extern "C" int afx_encrypt_dev(afx_ctx* ctx, const afx_keypairs_soa* kp, const uint8_t* M1, const uint8_t* M2, const uint8_t* m3, size_t count,
+                               uint8_t* E1, uint8_t* E2, uint8_t* status) try {
+  CtxLock lock__(ctx);
+  if (!ctx || !kp || !kp->a || !kp->a0 || !kp->a1 || !M1 || !M2 || !m3 || !E1 || !E2 || !status) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  if (count == 0) return AFX_OK;
+  return encrypt_on_device(ctx, kp->a, kp->a0, kp->a1, M1, M2, m3, count, E1, E2, status);
+} catch (...) { return afx::exception_rc(); }
 extern "C" int afx_encrypt(afx_ctx* ctx, const afx_keypairs_soa* kp, const uint8_t* M1, const uint8_t* M2, const uint8_t* m3, size_t count,
                            uint8_t* E1, uint8_t* E2, uint8_t* status) try {
   CtxLock lock__(ctx);
@@ -214,32 +247,14 @@ extern "C" int afx_encrypt(afx_ctx* ctx, const afx_keypairs_soa* kp, const uint8
                o_m3 = st.add(m3, row), o_E1 = st.add(nullptr, row), o_E2 = st.add(nullptr, row), o_st = st.add(nullptr, count);
   int rc = st.upload();
   if (rc) return rc;
-  rc = run_chunked(ctx, count, [&](Assembler& as, size_t off, uint32_t) {
-    as.secret_scalars = true;   // the user's symmetric key: afx_ctx_set_secret_independent_addressing
-    auto at = [&](size_t o) { return st.dev(o) + 32 * off; };
-    int32_t *v_M1 = as.new_var(), *v_M2 = as.new_var(), *v_E1 = as.new_var();
-    uint8_t* k = as.new_enc();
-    as.sccheck({ { at(o_a) }, { at(o_a0) }, { at(o_a1) }, { at(o_m3) } });
-    as.decode({ { at(o_M1), v_M1, 0 }, { at(o_M2), v_M2, 0 } });
-    as.scalarop({ mk_sop(at(o_a1), 32, at(o_m3), 32, at(o_a0), 32, k) });                                   // a0 + a1*m3
-    afx_msm_job jE1 = mk_msm({ mk_term(k, 32, v_M2, -1, false) }, nullptr, v_E1, at(o_E1));                   // E1 = M2*(a0 + a1*m3)
-    jE1.leave_half = 1;   // an output and the base of E2's term: plan.h afx_msm_job.leave_half
-    as.msm({ jE1 });
-    as.msm({ mk_msm({ mk_term(at(o_a), 32, v_E1, -1, false) }, v_M1, nullptr, at(o_E2)) });                   // E2 = E1*a + M1
-    as.finish(st.dev(o_st) + off, AFX_ST_VERIFICATION_FAILURE);
-  });
-  if (rc) return rc;
+  if ((rc = encrypt_on_device(ctx, st.dev(o_a), st.dev(o_a0), st.dev(o_a1), st.dev(o_M1), st.dev(o_M2), st.dev(o_m3), count, st.dev(o_E1), st.dev(o_E2), st.dev(o_st)))) return rc;
   AFX_HIP(hipMemcpyAsync(E1, st.dev(o_E1), row, hipMemcpyDeviceToHost, ctx->stream));
   AFX_HIP(hipMemcpyAsync(E2, st.dev(o_E2), row, hipMemcpyDeviceToHost, ctx->stream));
   return sync_fetch(ctx, status, st.dev(o_st), count);
 } catch (...) { return afx::exception_rc(); }
 
-extern "C" int afx_decrypt(afx_ctx* ctx, const afx_keypairs_soa* kp, const uint8_t* E1, const uint8_t* E2, size_t count, uint8_t* M1, uint8_t* M2,
-                           uint8_t* m3, uint8_t* messages, uint8_t* status) try {
-  CtxLock lock__(ctx);
-  if (!ctx || !kp || !kp->a || !kp->a0 || !kp->a1 || !E1 || !E2 || !M1 || !M2 || !m3 || !status) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  if (count == 0) return AFX_OK;
-  AFX_HIP(hipSetDevice(ctx->device));
+static int decrypt_without_hash_kernels(afx_ctx* ctx, const afx_keypairs_soa* kp, const uint8_t* E1, const uint8_t* E2, size_t count, uint8_t* M1, uint8_t* M2,
+                                        uint8_t* m3, uint8_t* messages, uint8_t* status) {
   const size_t row = 32 * count;
   int rc;
   std::vector<uint8_t> bad1(count), bad2(count), e1p(row), wide(64 * count);
@@ -295,5 +310,188 @@ extern "C" int afx_decrypt(afx_ctx* ctx, const afx_keypairs_soa* kp, const uint8
   // ciphertext.E1 == E1' : canonical encodings are equal iff the group elements are (symmetric.rs:285-288)
   for (size_t i = 0; i < count; i++)
     status[i] = (!bad1[i] && !bad2[i] && memcmp(e1p.data() + 32 * i, E1 + 32 * i, 32) == 0) ? AFX_ST_OK : AFX_ST_UNDECRYPTABLE;
+  return AFX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the four calls over device rows: one plan each
+// ------------------------------------------------------------------------------------------------
+static afx_sha512_job mk_sha(const uint8_t* src, uint32_t stride, uint32_t offset, uint32_t len, uint8_t* out, uint8_t* copy = nullptr) {
+  afx_sha512_job j;
+  memset(&j, 0, sizeof j);
+  j.src = src; j.out = out; j.copy = copy; j.stride = stride; j.offset = offset; j.len = len;
+  return j;
+}
+
+// impl From<&[u8; 30]> for Plaintext (symmetric.rs:135-143): wide = SHA-512(m); M2 = from_uniform_bytes(wide), m3 = wide mod l;
+// M1 = encode_to_group(m)
+static int plaintexts_on_device(afx_ctx* ctx, const uint8_t* msgs, size_t count, uint8_t* M1, uint8_t* M2, uint8_t* m3, uint32_t* counters, uint8_t* status) {
+  return run_chunked(ctx, count, [&](Assembler& as, size_t off, uint32_t) {
+    uint8_t* wide = as.new_wide();
+    as.sha512(mk_sha(msgs + 30 * off, 30, 0, 30, wide));
+    as.reduce_wide(wide, m3 + 32 * off);
+    as.from_uniform(wide, M2 + 32 * off, nullptr);
+    const afx_encode_job e = { msgs + 30 * off, M1 + 32 * off, counters ? counters + off : nullptr, M2 + 32 * off, m3 + 32 * off };
+    as.encode_to_group(e);
+    as.finish(status + off, AFX_ST_VERIFICATION_FAILURE);
+  });
+}
+extern "C" int afx_plaintexts_from_bytes_dev(afx_ctx* ctx, const uint8_t* msgs, size_t count, uint8_t* M1, uint8_t* M2, uint8_t* m3, uint32_t* counters, uint8_t* status) try {
+  CtxLock lock__(ctx);
+  if (!ctx || !msgs || !M1 || !M2 || !m3 || !status) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  if (count == 0) return AFX_OK;
+  int rc = need_hash_kernels();
+  if (rc) return rc;
+  return plaintexts_on_device(ctx, msgs, count, M1, M2, m3, counters, status);
+} catch (...) { return afx::exception_rc(); }
+extern "C" int afx_plaintexts_from_bytes(afx_ctx* ctx, const uint8_t* msgs, size_t count, uint8_t* M1, uint8_t* M2, uint8_t* m3, uint32_t* counters) try {
+  CtxLock lock__(ctx);
+  if (!ctx || !msgs || !M1 || !M2 || !m3) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  if (count == 0) return AFX_OK;
+  AFX_HIP(hipSetDevice(ctx->device));
+  if (!have_hash_kernels()) return plaintexts_without_hash_kernels(ctx, msgs, count, M1, M2, m3, counters);
+  // only the 30 message bytes go to the device
+  Stager st(ctx);
+  const size_t row = 32 * count;
+  const size_t o_msg = st.add(msgs, 30 * count), o_M1 = st.add(nullptr, row), o_M2 = st.add(nullptr, row), o_m3 = st.add(nullptr, row),
+               o_ctr = st.add(nullptr, 4 * count), o_st = st.add(nullptr, count);
+  int rc = st.upload();
+  if (rc) return rc;
+  if ((rc = plaintexts_on_device(ctx, st.dev(o_msg), count, st.dev(o_M1), st.dev(o_M2), st.dev(o_m3), (uint32_t*)st.dev(o_ctr), st.dev(o_st)))) return rc;
+  std::vector<uint8_t> status(count);
+  AFX_HIP(hipMemcpyAsync(M1, st.dev(o_M1), row, hipMemcpyDeviceToHost, ctx->stream));
+  AFX_HIP(hipMemcpyAsync(M2, st.dev(o_M2), row, hipMemcpyDeviceToHost, ctx->stream));
+  AFX_HIP(hipMemcpyAsync(m3, st.dev(o_m3), row, hipMemcpyDeviceToHost, ctx->stream));
+  if (counters) AFX_HIP(hipMemcpyAsync(counters, st.dev(o_ctr), 4 * count, hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = sync_fetch(ctx, status.data(), st.dev(o_st), count))) return rc;
+  for (size_t i = 0; i < count; i++)
+    if (status[i]) { set_error("encode_to_group found no representative (the reference panics)"); return AFX_E_BAD_ARGS; }
+  return AFX_OK;
+} catch (...) { return afx::exception_rc(); }
+
+// Keypair::derive (symmetric.rs:197-215): a = H(master), a0 = H(a), a1 = H(a0), each reduced mod l, as one chain; pk = a*G_a + a0*G_a0 + a1*G_a1
+static int derive_on_device(afx_ctx* ctx, const uint8_t* master_secrets, size_t count, uint8_t* a, uint8_t* a0, uint8_t* a1, uint8_t* pk) {
+  return run_chunked(ctx, count, [&](Assembler& as, size_t off, uint32_t) {
+    as.secret_scalars = true;   // the user's symmetric key: afx_ctx_set_secret_independent_addressing
+    afx_ctx* c = as.ctx;
+    uint8_t* wide = as.new_wide();   // the three hashes that reduce to the secret keys, one after the other
+    uint8_t *pa = a + 32 * off, *pa0 = a0 + 32 * off, *pa1 = a1 + 32 * off;
+    as.sha512(mk_sha(master_secrets + 64 * off, 64, 0, 64, wide));
+    as.reduce_wide(wide, pa);
+    as.sha512(mk_sha(pa, 32, 0, 32, wide));
+    as.reduce_wide(wide, pa0);
+    as.sha512(mk_sha(pa0, 32, 0, 32, wide));
+    as.reduce_wide(wide, pa1);
+    as.wipe(wide, 64);
+    as.msm({ mk_msm({ mk_term(pa, 32, nullptr, (int32_t)c->id_Ga(), false), mk_term(pa0, 32, nullptr, (int32_t)c->id_Ga0(), false),
+                      mk_term(pa1, 32, nullptr, (int32_t)c->id_Ga1(), false) }, nullptr, nullptr, pk + 32 * off) });
+    as.finish(as.new_enc(), 1);   // (nothing here can fail an item: the status bytes stay in the workspace)
+  });
+}
+extern "C" int afx_keypairs_derive_dev(afx_ctx* ctx, const uint8_t* master_secrets, size_t count, uint8_t* a, uint8_t* a0, uint8_t* a1, uint8_t* pk) try {
+  CtxLock lock__(ctx);
+  if (!ctx || !master_secrets || !a || !a0 || !a1 || !pk) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  if (count == 0) return AFX_OK;
+  int rc = need_hash_kernels();
+  if (rc) return rc;
+  return derive_on_device(ctx, master_secrets, count, a, a0, a1, pk);
+} catch (...) { return afx::exception_rc(); }
+extern "C" int afx_keypairs_derive(afx_ctx* ctx, const uint8_t* master_secrets, size_t count, uint8_t* a, uint8_t* a0, uint8_t* a1, uint8_t* pk) try {
+  CtxLock lock__(ctx);
+  if (!ctx || !master_secrets || !a || !a0 || !a1 || !pk) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  if (count == 0) return AFX_OK;
+  AFX_HIP(hipSetDevice(ctx->device));
+  if (!have_hash_kernels()) return derive_without_hash_kernels(ctx, master_secrets, count, a, a0, a1, pk);
+  Stager st(ctx);
+  const size_t row = 32 * count;
+  const size_t o_ms = st.add(master_secrets, 64 * count), o_a = st.add(nullptr, row), o_a0 = st.add(nullptr, row), o_a1 = st.add(nullptr, row), o_pk = st.add(nullptr, row);
+  int rc = st.upload();
+  if (rc) return rc;
+  if ((rc = derive_on_device(ctx, st.dev(o_ms), count, st.dev(o_a), st.dev(o_a0), st.dev(o_a1), st.dev(o_pk)))) return rc;
+  AFX_HIP(hipMemcpyAsync(a, st.dev(o_a), row, hipMemcpyDeviceToHost, ctx->stream));
+  AFX_HIP(hipMemcpyAsync(a0, st.dev(o_a0), row, hipMemcpyDeviceToHost, ctx->stream));
+  AFX_HIP(hipMemcpyAsync(a1, st.dev(o_a1), row, hipMemcpyDeviceToHost, ctx->stream));
+  return sync_fetch(ctx, pk, st.dev(o_pk), row);
+} catch (...) { return afx::exception_rc(); }
+
+// Keypair::decrypt (symmetric.rs:273-289): M1' = E2 - a*E1; m' = bytes 1..30 of its encoding (decode_from_group, encoding.rs:75-82);
+// wide = SHA-512(m'), m3' = wide mod l, M2' = from_uniform_bytes(wide); E1' = (a0 + a1*m3')*M2'; the item decrypts iff E1 - E1' is the
+// identity
+static int decrypt_on_device(afx_ctx* ctx, const uint8_t* a, const uint8_t* a0, const uint8_t* a1, const uint8_t* E1, const uint8_t* E2, size_t count, uint8_t* M1,
+                             uint8_t* M2, uint8_t* m3, uint8_t* messages, uint8_t* status) {
+  return run_chunked(ctx, count, [&](Assembler& as, size_t off, uint32_t) {
+    as.secret_scalars = true;   // the user's symmetric key: afx_ctx_set_secret_independent_addressing
+    int32_t *v_E1 = as.new_var(), *v_E2 = as.new_var(), *v_M2 = as.new_var(), *v_E1p = as.new_var();
+    uint8_t *wide = as.new_wide(), *k = as.new_enc(), *diff = as.new_enc();
+    uint8_t *pM1 = M1 + 32 * off, *pM2 = M2 + 32 * off, *pm3 = m3 + 32 * off;
+    as.sccheck({ { a + 32 * off }, { a0 + 32 * off }, { a1 + 32 * off } });
+    as.decode({ { E1 + 32 * off, v_E1, 0 }, { E2 + 32 * off, v_E2, 0 } });
+    as.msm({ mk_msm({ mk_term(a + 32 * off, 32, v_E1, -1, true) }, v_E2, nullptr, pM1) });
+    as.sha512(mk_sha(pM1, 32, 1, 30, wide, messages ? messages + 30 * off : nullptr));
+    as.reduce_wide(wide, pm3);
+    as.from_uniform(wide, pM2, v_M2);
+    as.scalarop({ mk_sop(a1 + 32 * off, 32, pm3, 32, a0 + 32 * off, 32, k) });
+    as.msm({ mk_msm({ mk_term(k, 32, v_M2, -1, false) }, nullptr, v_E1p, nullptr) });
+    afx_pointop_job eq;
+    memset(&eq, 0, sizeof eq);
+    eq.a = v_E1; eq.b = v_E1p; eq.sa = 1; eq.sb = -1; eq.out_enc = diff; eq.reject_identity = 2;   // ciphertext.E1 == E1' (symmetric.rs:285-288)
+    as.pointop({ eq });
+    as.wipe(wide, 64);   // the hash of the recovered plaintext
+    as.wipe(k, 32);      // a0 + a1*m3'
+    as.finish(status + off, AFX_ST_UNDECRYPTABLE);
+  });
+}
+extern "C" int afx_decrypt_dev(afx_ctx* ctx, const afx_keypairs_soa* kp, const uint8_t* E1, const uint8_t* E2, size_t count, uint8_t* M1, uint8_t* M2,
+                               uint8_t* m3, uint8_t* messages, uint8_t* status) try {
+  CtxLock lock__(ctx);
+  if (!ctx || !kp || !kp->a || !kp->a0 || !kp->a1 || !E1 || !E2 || !M1 || !M2 || !m3 || !status) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  if (count == 0) return AFX_OK;
+  int rc = need_hash_kernels();
+  if (rc) return rc;
+  return decrypt_on_device(ctx, kp->a, kp->a0, kp->a1, E1, E2, count, M1, M2, m3, messages, status);
+} catch (...) { return afx::exception_rc(); }
+extern "C" int afx_decrypt(afx_ctx* ctx, const afx_keypairs_soa* kp, const uint8_t* E1, const uint8_t* E2, size_t count, uint8_t* M1, uint8_t* M2,
+                           uint8_t* m3, uint8_t* messages, uint8_t* status) try {
+  CtxLock lock__(ctx);
+  if (!ctx || !kp || !kp->a || !kp->a0 || !kp->a1 || !E1 || !E2 || !M1 || !M2 || !m3 || !status) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  if (count == 0) return AFX_OK;
+  AFX_HIP(hipSetDevice(ctx->device));
+  if (!have_hash_kernels()) return decrypt_without_hash_kernels(ctx, kp, E1, E2, count, M1, M2, m3, messages, status);
+  Stager st(ctx);
+  const size_t row = 32 * count;
+  const size_t o_a = st.add(kp->a, row), o_a0 = st.add(kp->a0, row), o_a1 = st.add(kp->a1, row), o_E1 = st.add(E1, row), o_E2 = st.add(E2, row),
+               o_M1 = st.add(nullptr, row), o_M2 = st.add(nullptr, row), o_m3 = st.add(nullptr, row), o_msg = st.add(nullptr, messages ? 30 * count : 0),
+               o_st = st.add(nullptr, count);
+  int rc = st.upload();
+  if (rc) return rc;
+  if ((rc = decrypt_on_device(ctx, st.dev(o_a), st.dev(o_a0), st.dev(o_a1), st.dev(o_E1), st.dev(o_E2), count, st.dev(o_M1), st.dev(o_M2), st.dev(o_m3),
+                              messages ? st.dev(o_msg) : nullptr, st.dev(o_st)))) return rc;
+  AFX_HIP(hipMemcpyAsync(M1, st.dev(o_M1), row, hipMemcpyDeviceToHost, ctx->stream));
+  AFX_HIP(hipMemcpyAsync(M2, st.dev(o_M2), row, hipMemcpyDeviceToHost, ctx->stream));
+  AFX_HIP(hipMemcpyAsync(m3, st.dev(o_m3), row, hipMemcpyDeviceToHost, ctx->stream));
+  if (messages) AFX_HIP(hipMemcpyAsync(messages, st.dev(o_msg), 30 * count, hipMemcpyDeviceToHost, ctx->stream));
+  return sync_fetch(ctx, status, st.dev(o_st), count);
+} catch (...) { return afx::exception_rc(); }
+
+// SHA-512 over a batch of equally long messages (a batch primitive beside afx_merlin_challenges: published vectors on the device's
+// own SHA-512)
+extern "C" int afx_sha512(afx_ctx* ctx, const uint8_t* msgs, size_t msg_len, size_t count, uint8_t* out) try {
+  CtxLock lock__(ctx);
+  if (!ctx || !out || (!msgs && msg_len && count)) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  if (msg_len > 1024) { set_error("afx_sha512: messages of at most 1024 bytes"); return AFX_E_BAD_ARGS; }
+  if (count == 0) return AFX_OK;
+  int rc = need_hash_kernels();
+  if (rc) return rc;
+  AFX_HIP(hipSetDevice(ctx->device));
+  const size_t chunk = ctx->chunk_items ? ctx->chunk_items : CHUNK_DEFAULT;
+  static const uint8_t none[4] = { 0 };
+  for (size_t off = 0; off < count; off += chunk) {
+    const size_t n = std::min(chunk, count - off);
+    Stager st(ctx);
+    const size_t o_in = st.add(msg_len ? msgs + msg_len * off : none, msg_len ? msg_len * n : sizeof none), o_out = st.add(nullptr, 64 * n);
+    if ((rc = st.upload())) return rc;
+    AFX_HIP(afxk_sha512(ctx->stream, st.dev(o_in), (uint32_t)msg_len, 0, (uint32_t)msg_len, st.dev(o_out), (uint32_t)n));
+    if ((rc = sync_fetch(ctx, out + 64 * off, st.dev(o_out), 64 * n))) return rc;
+  }
   return AFX_OK;
 } catch (...) { return afx::exception_rc(); }

@@ -826,17 +826,45 @@ int afx_issuer_keygen(int device, const uint8_t* sysparams, size_t sysparams_len
  * AFX_E_BAD_ARGS if the stream runs out, AFX_E_BAD_PARAMS for CredentialError::NoSystemParameters (duplicates). */
 int afx_system_parameters_generate(int device, uint32_t n_attributes, const uint8_t* rng_stream, size_t stream_len,
                                    uint8_t* params_out, size_t params_cap, size_t* consumed_out);
+/* ---- application data <-> attributes: plaintexts, keypairs, encryption, decryption ------------
+ * Each of the four is ONE plan on the device - SHA-512 (k_sha512), encode_to_group's counter search (k_encode_to_group), Elligator,
+ * the reductions and the multiscalar chains - in a host-pointer form, which stages its rows once and fetches once, and a *_dev
+ * form: every pointer a device pointer (rows 16-byte aligned, counters 4-byte), the call asynchronous on afx_ctx_stream.  Counts
+ * beyond afx_ctx_set_chunk_items run as several passes.  Rows that hold key material or a recovered plaintext on the way (the
+ * wide hashes of the derive chain; decrypt's hash of the recovered message and a0 + a1*m3') are zeroed on the device, in stream
+ * order, before the call completes. */
+
 /* impl From<&[u8; 30]> for Plaintext (src/symmetric.rs:135-143): M1 = encode_to_group (src/encoding.rs:56-70; counter out),
- * M2 = hash-to-group, m3 = hash-to-scalar.  msgs [count][30]; SHA-512 runs on the host, everything else on the GPU. */
+ * M2 = hash-to-group, m3 = hash-to-scalar of SHA-512(msg).  msgs [count][30]: the only bytes that go to the device.
+ * encode_to_group tries the counters 0 .. 8191 in the reference's order until a candidate decodes: ITS TRIP COUNT DEPENDS ON THE
+ * MESSAGE, exactly as the reference's loop does (four tries on average; a lane per message).  counters may be NULL.
+ * A message none of whose candidates decodes (the reference panics; probability (3/4)^8192): the host form returns AFX_E_BAD_ARGS,
+ * the _dev form gives the item AFX_ST_VERIFICATION_FAILURE and zeroed outputs. */
 int afx_plaintexts_from_bytes(afx_ctx* ctx, const uint8_t* msgs, size_t count, uint8_t* M1, uint8_t* M2, uint8_t* m3, uint32_t* counters);
-/* Keypair::derive (src/symmetric.rs:197-215): master_secrets [count][64] -> a, a0, a1, pk ([count][32] each). */
+int afx_plaintexts_from_bytes_dev(afx_ctx* ctx, const uint8_t* msgs, size_t count, uint8_t* M1, uint8_t* M2, uint8_t* m3, uint32_t* counters /* or NULL */,
+                                  uint8_t* status);
+/* Keypair::derive (src/symmetric.rs:197-215): master_secrets [count][64] -> a, a0, a1, pk ([count][32] each).  The three hashes
+ * and reductions run as one chain on the device; pk under the context's secret-independent addressing. */
 int afx_keypairs_derive(afx_ctx* ctx, const uint8_t* master_secrets, size_t count, uint8_t* a, uint8_t* a0, uint8_t* a1, uint8_t* pk);
-/* Keypair::encrypt (src/symmetric.rs:252-261) and Keypair::decrypt (:273-289; status AFX_ST_UNDECRYPTABLE on mismatch;
- * `messages` [count][30] = decode_from_group of the recovered M1, may be NULL). */
+int afx_keypairs_derive_dev(afx_ctx* ctx, const uint8_t* master_secrets, size_t count, uint8_t* a, uint8_t* a0, uint8_t* a1, uint8_t* pk);
+/* Keypair::encrypt (src/symmetric.rs:252-261): status AFX_ST_VERIFICATION_FAILURE for a non-canonical scalar or an M1 / M2 that does
+ * not decode.  keypairs->pk is not read. */
 int afx_encrypt(afx_ctx* ctx, const afx_keypairs_soa* keypairs, const uint8_t* M1, const uint8_t* M2, const uint8_t* m3, size_t count,
                 uint8_t* E1, uint8_t* E2, uint8_t* status);
+int afx_encrypt_dev(afx_ctx* ctx, const afx_keypairs_soa* keypairs, const uint8_t* M1, const uint8_t* M2, const uint8_t* m3, size_t count,
+                    uint8_t* E1, uint8_t* E2, uint8_t* status);
+/* Keypair::decrypt (src/symmetric.rs:273-289): M1' = E2 - a*E1, m' = bytes 1..30 of its encoding (decode_from_group), m3' and M2'
+ * from SHA-512(m'), E1' = (a0 + a1*m3')*M2'; status AFX_ST_UNDECRYPTABLE unless E1 - E1' is the identity (and for inputs that do not
+ * decode or are not canonical).  M1, M2, m3 receive M1', M2', m3' for every item; `messages` [count][30] = m', may be NULL.
+ * keypairs->pk is not read. */
 int afx_decrypt(afx_ctx* ctx, const afx_keypairs_soa* keypairs, const uint8_t* E1, const uint8_t* E2, size_t count, uint8_t* M1,
                 uint8_t* M2, uint8_t* m3, uint8_t* messages, uint8_t* status);
+int afx_decrypt_dev(afx_ctx* ctx, const afx_keypairs_soa* keypairs, const uint8_t* E1, const uint8_t* E2, size_t count, uint8_t* M1,
+                    uint8_t* M2, uint8_t* m3, uint8_t* messages /* or NULL */, uint8_t* status);
+
+/* SHA-512 (FIPS 180-4) of `count` messages of msg_len bytes each (0 .. 1024; longer: AFX_E_BAD_ARGS), out [count][64]: the kernel the
+ * four calls above hash with, as a batch primitive - published vectors run on the device.  Host pointers. */
+int afx_sha512(afx_ctx* ctx, const uint8_t* msgs /*[count][msg_len]*/, size_t msg_len, size_t count, uint8_t* out /*[count][64]*/);
 
 /* Batch ristretto255 primitives (dalek CompressedRistretto::decompress -> compress round trip,
  * RistrettoPoint::from_uniform_bytes, Scalar::from_bytes_mod_order_wide); used to build synthetic
