@@ -117,6 +117,25 @@ class CommitmentsSoA(C.Structure):
     _fields_ = [("main", C.c_void_p), ("enc", C.POINTER(C.c_void_p))]
 
 
+class BlindRequestRandomness(C.Structure):
+    """afx_blind_request_randomness (include/aeonflux_gpu.h "Blind issuance")"""
+    _fields_ = [(k, C.c_void_p) for k in ("r_wide", "rng_seed")]
+
+
+class BlindRequestSoA(C.Structure):
+    """afx_blind_request_soa: D [count], A, B [h][count], challenge [count], responses [1 + h + hs][count]"""
+    _fields_ = [(k, C.c_void_p) for k in ("D", "A", "B", "challenge", "responses")]
+
+
+class BlindIssueRandomness(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("t_wide", "U_wide", "rprime_wide", "rng_seed")]
+
+
+class BlindIssuanceSoA(C.Structure):
+    """afx_blind_issuance_soa: t, U, S1, S2, challenge [count], responses [n + 6][count]"""
+    _fields_ = [(k, C.c_void_p) for k in ("t", "U", "S1", "S2", "challenge", "responses")]
+
+
 def DRAW_ENC_SEED(j):
     return 5 + j
 
@@ -185,6 +204,17 @@ def lib():
             _LIB.afx_keypairs_derive_dev.argtypes = _LIB.afx_keypairs_derive.argtypes
             _LIB.afx_encrypt_dev.argtypes = _LIB.afx_encrypt.argtypes
             _LIB.afx_decrypt_dev.argtypes = _LIB.afx_decrypt.argtypes
+        # (blind issuance)
+        if hasattr(_LIB, "afx_issue_blind"):
+            for sfx in ("", "_dev"):
+                getattr(_LIB, "afx_blind_request" + sfx).argtypes = [C.c_void_p, C.POINTER(AttributesSoA), C.c_void_p, C.POINTER(BlindRequestRandomness), C.c_size_t,
+                                                                    C.POINTER(BlindRequestSoA), C.c_void_p]
+                getattr(_LIB, "afx_verify_blind_requests" + sfx).argtypes = [C.c_void_p, C.POINTER(AttributesSoA), C.POINTER(BlindRequestSoA), C.c_uint32, C.c_size_t,
+                                                                            C.c_void_p]
+                getattr(_LIB, "afx_issue_blind" + sfx).argtypes = [C.c_void_p, C.POINTER(AttributesSoA), C.POINTER(BlindRequestSoA), C.c_uint32,
+                                                                  C.POINTER(BlindIssueRandomness), C.c_size_t, C.POINTER(BlindIssuanceSoA), C.c_void_p]
+                getattr(_LIB, "afx_unblind_issuances" + sfx).argtypes = [C.c_void_p, C.POINTER(AttributesSoA), C.c_void_p, C.POINTER(BlindRequestSoA),
+                                                                        C.POINTER(BlindIssuanceSoA), C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]
         _LIB.afx_wire_header_bytes.restype = C.c_size_t
         _LIB.afx_wire_header_bytes.argtypes = [C.POINTER(Shape)]
         _LIB.afx_wire_cells_per_record.restype = C.c_uint32

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import (AttributesSoA, CommitmentsSoA, CredentialsSoA, DeviceRng, EncProofOut, EncProofSoA, IssuanceGroup, IssuanceSoA, IssueGroup, IssueRandomness, KeypairsSoA,
+from . import (AttributesSoA, BlindIssuanceSoA, BlindIssueRandomness, BlindRequestRandomness, BlindRequestSoA, CommitmentsSoA, CredentialsSoA, DeviceRng, EncProofOut, EncProofSoA, IssuanceGroup, IssuanceSoA, IssueGroup, IssueRandomness, KeypairsSoA,
                PresentationOut, PresentationSoA, Shape, ShowGroup, ShowRandomness, check, lib)
 
 ENC_FIELDS = ("challenge", "responses", "pk", "E1", "E2", "C_y_1", "C_y_2", "C_y_3", "C_y_2p")
@@ -412,6 +412,120 @@ def decrypt_dev(ctx, keypairs, E1, E2, count, M1, M2, m3, messages, status):
     """afx_decrypt_dev: messages ([count][30]) may be None"""
     soa = _keypairs_soa(keypairs, _dptr)
     check(lib().afx_decrypt_dev(ctx.h, C.byref(soa), _dptr(E1), _dptr(E2), count, _dptr(M1), _dptr(M2), _dptr(m3), _dptr(messages), _dptr(status)))
+
+
+# ---- blind issuance (include/aeonflux_gpu.h "Blind issuance") ----
+REQUEST_FIELDS = ("D", "A", "B", "challenge", "responses")
+BLIND_ISSUANCE_FIELDS = ("t", "U", "S1", "S2", "challenge", "responses")
+
+
+def blind_layout(kinds):
+    """(h, hs): hidden positions of a layout and how many of them are scalars; a request has 1 + h + hs responses"""
+    return sum(1 for k in kinds if k in (1, 4)), sum(1 for k in kinds if k == 1)
+
+
+def _blind_attrs(kinds, values, ptr):
+    s = AttributesSoA()
+    s.n_attributes = len(kinds)
+    for i, k in enumerate(kinds[:len(s.kinds)]):
+        s.kinds[i] = k
+    s.values = ptr(values) if values is not None else None
+    return s
+
+
+def _hptr(a):
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def blind_request(ctx, kinds, values, d, r_wide, rng_seed):
+    """afx_blind_request: values [n, count, 32], d [count, 32], r_wide [h, count, 64], rng_seed [count, 32]
+    -> (dict(D, A [h], B [h], challenge, responses [1 + h + hs]), status [count])"""
+    values, d, r_wide, rng_seed = map(_u8, (values, d, r_wide, rng_seed))
+    cnt = d.shape[0]
+    h, hs = blind_layout(kinds)
+    o = dict(D=np.zeros((cnt, 32), np.uint8), A=np.zeros((h, cnt, 32), np.uint8), B=np.zeros((h, cnt, 32), np.uint8), challenge=np.zeros((cnt, 32), np.uint8),
+             responses=np.zeros((1 + h + hs, cnt, 32), np.uint8))
+    status = np.full(cnt, 255, np.uint8)
+    a = _blind_attrs(kinds, values, _hptr)
+    rnd = BlindRequestRandomness(_hptr(r_wide), _hptr(rng_seed))
+    out = BlindRequestSoA(*(_hptr(o[f]) for f in REQUEST_FIELDS))
+    check(lib().afx_blind_request(ctx.h, C.byref(a), _hptr(d), C.byref(rnd), cnt, C.byref(out), status.ctypes.data))
+    return o, status
+
+
+def verify_blind_requests(ctx, kinds, request, n_responses=None):
+    """afx_verify_blind_requests -> status [count]"""
+    q = {f: _u8(request[f]) for f in REQUEST_FIELDS}
+    cnt = q["D"].shape[0]
+    status = np.full(cnt, 255, np.uint8)
+    a = _blind_attrs(kinds, None, _hptr)
+    soa = BlindRequestSoA(*(_hptr(q[f]) for f in REQUEST_FIELDS))
+    nr = q["responses"].shape[0] if n_responses is None else n_responses
+    check(lib().afx_verify_blind_requests(ctx.h, C.byref(a), C.byref(soa), nr, cnt, status.ctypes.data))
+    return status
+
+
+def issue_blind(ctx, kinds, values, request, t_wide, U_wide, rprime_wide, rng_seed, request_n_responses=None):
+    """afx_issue_blind: values [n, count, 32] (the rows of hidden positions are never read), request as blind_request returned it
+    -> (dict(t, U, S1, S2, challenge, responses [n + 6]), status [count])"""
+    values, t_wide, U_wide, rprime_wide, rng_seed = map(_u8, (values, t_wide, U_wide, rprime_wide, rng_seed))
+    q = {f: _u8(request[f]) for f in REQUEST_FIELDS}
+    cnt = t_wide.shape[0]
+    o = {f: np.zeros((cnt, 32), np.uint8) for f in BLIND_ISSUANCE_FIELDS[:5]}
+    o["responses"] = np.zeros((ctx.n + 6, cnt, 32), np.uint8)
+    status = np.full(cnt, 255, np.uint8)
+    a = _blind_attrs(kinds, values, _hptr)
+    soa = BlindRequestSoA(*(_hptr(q[f]) for f in REQUEST_FIELDS))
+    rnd = BlindIssueRandomness(*(_hptr(x) for x in (t_wide, U_wide, rprime_wide, rng_seed)))
+    out = BlindIssuanceSoA(*(_hptr(o[f]) for f in BLIND_ISSUANCE_FIELDS))
+    nr = q["responses"].shape[0] if request_n_responses is None else request_n_responses
+    check(lib().afx_issue_blind(ctx.h, C.byref(a), C.byref(soa), nr, C.byref(rnd), cnt, C.byref(out), status.ctypes.data))
+    return o, status
+
+
+def unblind_issuances(ctx, kinds, values, d, request, issuance, n_responses=None):
+    """afx_unblind_issuances: the user's own request (D, A, B) and d, the issuer's answer -> (V [count, 32], status [count])"""
+    values, d = _u8(values), _u8(d)
+    q = {f: _u8(request[f]) for f in ("D", "A", "B")}
+    s = {f: _u8(issuance[f]) for f in BLIND_ISSUANCE_FIELDS}
+    cnt = d.shape[0]
+    V = np.zeros((cnt, 32), np.uint8)
+    status = np.full(cnt, 255, np.uint8)
+    a = _blind_attrs(kinds, values, _hptr)
+    soa = BlindRequestSoA(_hptr(q["D"]), _hptr(q["A"]), _hptr(q["B"]), None, None)
+    iss = BlindIssuanceSoA(*(_hptr(s[f]) for f in BLIND_ISSUANCE_FIELDS))
+    nr = s["responses"].shape[0] if n_responses is None else n_responses
+    check(lib().afx_unblind_issuances(ctx.h, C.byref(a), _hptr(d), C.byref(soa), C.byref(iss), nr, cnt, V.ctypes.data, status.ctypes.data))
+    return V, status
+
+
+def blind_request_dev(ctx, kinds, values, d, r_wide, rng_seed, count, out, status):
+    """afx_blind_request_dev: device rows; out = dict(D, A, B, challenge, responses) of device rows (A, B may be None when h == 0)"""
+    a = _blind_attrs(kinds, values, _dptr)
+    rnd = BlindRequestRandomness(_dptr(r_wide), _dptr(rng_seed))
+    soa = BlindRequestSoA(*(_dptr(out.get(f)) for f in REQUEST_FIELDS))
+    check(lib().afx_blind_request_dev(ctx.h, C.byref(a), _dptr(d), C.byref(rnd), count, C.byref(soa), _dptr(status)))
+
+
+def verify_blind_requests_dev(ctx, kinds, request, n_responses, count, status):
+    a = _blind_attrs(kinds, None, _dptr)
+    soa = BlindRequestSoA(*(_dptr(request.get(f)) for f in REQUEST_FIELDS))
+    check(lib().afx_verify_blind_requests_dev(ctx.h, C.byref(a), C.byref(soa), n_responses, count, _dptr(status)))
+
+
+def issue_blind_dev(ctx, kinds, values, request, request_n_responses, t_wide, U_wide, rprime_wide, rng_seed, count, out, status):
+    a = _blind_attrs(kinds, values, _dptr)
+    soa = BlindRequestSoA(*(_dptr(request.get(f)) for f in REQUEST_FIELDS))
+    rnd = BlindIssueRandomness(*(_dptr(x) for x in (t_wide, U_wide, rprime_wide, rng_seed)))
+    o = BlindIssuanceSoA(*(_dptr(out.get(f)) for f in BLIND_ISSUANCE_FIELDS))
+    check(lib().afx_issue_blind_dev(ctx.h, C.byref(a), C.byref(soa), request_n_responses, C.byref(rnd), count, C.byref(o), _dptr(status)))
+
+
+def unblind_issuances_dev(ctx, kinds, values, d, request, issuance, n_responses, count, V, status):
+    a = _blind_attrs(kinds, values, _dptr)
+    soa = BlindRequestSoA(_dptr(request.get("D")), _dptr(request.get("A")), _dptr(request.get("B")), None, None)
+    iss = BlindIssuanceSoA(*(_dptr(issuance.get(f)) for f in BLIND_ISSUANCE_FIELDS))
+    check(lib().afx_unblind_issuances_dev(ctx.h, C.byref(a), _dptr(d), C.byref(soa), C.byref(iss), n_responses, count, _dptr(V), _dptr(status)))
 
 
 def multiscalar_mul(ctx, scalars, points):

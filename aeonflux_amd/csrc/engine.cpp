@@ -12,6 +12,8 @@
 // (a weak reference, like afxk_draw in plans.cpp: the host simulation builds of the engine link the launchers they need from
 // tests/hostsim, and only the batchable simulation brings this one)
 hipError_t afxk_coef(hipStream_t s, const afx_coef_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
+// (likewise: only the blind-issuance simulation, tests/hostsim/fake_blind.cpp, brings this one)
+hipError_t afxk_mask_rows(hipStream_t s, const afx_mask_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
 // (likewise: only the plaintext simulation, tests/hostsim/fake_plaintext.cpp, brings these two)
 hipError_t afxk_sha512_jobs(hipStream_t s, const afx_sha512_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
 hipError_t afxk_encode_to_group(hipStream_t s, const afx_encode_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
@@ -104,6 +106,7 @@ uint8_t* Assembler::ws_alloc(size_t bytes) {
 int32_t* Assembler::new_var() { return (int32_t*)ws_alloc(sizeof(int32_t) * AFX_VAR_DWORDS * (size_t)count); }
 uint8_t* Assembler::new_enc() { return ws_alloc(32 * (size_t)count); }
 uint8_t* Assembler::new_wide() { return ws_alloc(64 * (size_t)count); }
+uint8_t* Assembler::new_rows(size_t rows) { return ws_alloc(32 * rows * (size_t)count); }
 uint64_t* Assembler::new_state() { return (uint64_t*)ws_alloc(sizeof(uint64_t) * 25 * (size_t)count); }
 size_t Assembler::blob_alloc(size_t bytes, size_t align) {
   const size_t off = (blob_.size() + align - 1) & ~(align - 1);
@@ -995,6 +998,13 @@ void Assembler::copy(uint8_t* dst, const uint8_t* src, size_t bytes) {
   Launch l; l.kind = L_COPY; l.in = src; l.out = dst; l.bytes = bytes;
   launches.push_back(l);
 }
+void Assembler::mask(const std::vector<uint8_t*>& rows) {
+  flush_maps();
+  flush_encodings();   // (the rows' last writers may be encodings a small pass still has queued)
+  std::vector<afx_mask_job> jobs;
+  for (uint8_t* r : rows) if (r) { const afx_mask_job j = { r }; jobs.push_back(j); }
+  add_jobs(L_MASK, jobs);
+}
 void Assembler::finish(uint8_t* status_dev, uint8_t fail_code) {
   flush_maps();
   flush_encodings();   // (results no transcript reads; their rejections are flags k_finish folds into the status)
@@ -1074,6 +1084,7 @@ size_t job_size(LaunchKind k) {
     case L_COEF: return sizeof(afx_coef_job);
     case L_SHA512: return sizeof(afx_sha512_job);
     case L_ENCODE: return sizeof(afx_encode_job);
+    case L_MASK: return sizeof(afx_mask_job);
     default: return 0;
   }
 }
@@ -1140,6 +1151,7 @@ void Plan::relocate(uint8_t* nblob, uint8_t* nws, uint8_t* nin, uint8_t* nout) {
       case L_COEF: for (uint32_t i = 0; i < l.njobs; i++) { afx_coef_job& j = ((afx_coef_job*)J)[i]; m.fix(j.weights); m.fix(j.triples); m.fix(j.operands); m.fix(j.out); } break;
       case L_SHA512: for (uint32_t i = 0; i < l.njobs; i++) { afx_sha512_job& j = ((afx_sha512_job*)J)[i]; m.fix(j.src); m.fix(j.out); m.fix(j.copy); } break;
       case L_ENCODE: for (uint32_t i = 0; i < l.njobs; i++) { afx_encode_job& j = ((afx_encode_job*)J)[i]; m.fix(j.msgs); m.fix(j.M1); m.fix(j.counters); m.fix(j.zero_a); m.fix(j.zero_b); } break;
+      case L_MASK: for (uint32_t i = 0; i < l.njobs; i++) m.fix(((afx_mask_job*)J)[i].p); break;
       case L_COPY: m.fix(l.in); m.fix(l.out); break;
       case L_KINDS: break;
     }
@@ -1362,6 +1374,10 @@ int run_plans(afx_ctx* ctx, int lane, Plan* const* plans, size_t n) {
       case L_ENCODE:
         if (!afxk_encode_to_group) { set_error("no k_encode_to_group launcher in this build"); return AFX_E_NO_DEVICE; }
         AFX_HIP(afxk_encode_to_group(s, (const afx_encode_job*)jobs, nrows, rw, passes, max_count));
+        break;
+      case L_MASK:
+        if (!afxk_mask_rows) { set_error("no k_mask_rows launcher in this build"); return AFX_E_NO_DEVICE; }
+        AFX_HIP(afxk_mask_rows(s, (const afx_mask_job*)jobs, nrows, rw, passes, max_count));
         break;
       case L_MSM_TABLES: AFX_HIP(afxk_msm_tables(s, odd, (const afx_table_job*)jobs, nrows, rw, passes, max_count)); break;
       case L_MSM_FIXED: case L_MSM_WINDOW: case L_MSM_NAF: {

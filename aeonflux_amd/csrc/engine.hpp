@@ -267,7 +267,7 @@ namespace afx {
 
 // L_MSM_WINDOW keeps the slot the single k_msm kernel had (timing names: statements.cpp KIND_NAMES)
 enum LaunchKind { L_FILL_BAD, L_DECODE, L_SCCHECK, L_POINTOP, L_SCALAROP, L_MSM_WINDOW, L_HASH, L_FROM_UNIFORM, L_REDUCE_WIDE, L_COPY, L_FINISH,
-                  L_MSM_FIXED, L_MSM_NAF, L_MSM_TABLES, L_COMPRESS, L_POINTSUM, L_NEGENC, L_TABLE_AFFINE, L_POWERS, L_COEF, L_SHA512, L_ENCODE, L_KINDS };
+                  L_MSM_FIXED, L_MSM_NAF, L_MSM_TABLES, L_COMPRESS, L_POINTSUM, L_NEGENC, L_TABLE_AFFINE, L_POWERS, L_COEF, L_SHA512, L_ENCODE, L_MASK, L_KINDS };
 // the kernels whose grid rows WALK a range of the launch's jobs (afx_walk_row) instead of taking one job each (afx_row)
 inline bool walks(LaunchKind k) { return k == L_COMPRESS || k == L_NEGENC || k == L_TABLE_AFFINE; }
 
@@ -340,6 +340,7 @@ class Assembler {
   int32_t* new_var();         // extended point, SoA [36][count]
   uint8_t* new_enc();         // [count][32]
   uint8_t* new_wide();        // [count][64]
+  uint8_t* new_rows(size_t rows);   // [rows][count][32] in one piece (rows that one wipe() zeroes together)
   uint64_t* new_state();      // [25][count]
   size_t blob_bytes() const { return blob_.size(); }
 
@@ -361,6 +362,8 @@ class Assembler {
   void encode_to_group(const afx_encode_job& job);    // M1 = encode_to_group(msgs) (plan.h afx_encode_job); runs behind everything queued
   void wipe(void* p, size_t bytes_per_item);          // zeroes a [count][bytes_per_item] array of the pass in stream order (a multiple of 4 bytes)
   void copy(uint8_t* dst, const uint8_t* src, size_t bytes);   // device-to-device
+  void mask(const std::vector<uint8_t*>& rows);       // [count][32] output rows: the cells of items that have failed so far become zeros (k_mask_rows);
+                                                      // runs behind everything queued, call it right before finish()
   void finish(uint8_t* status_dev, uint8_t fail_code);
 
   // blob: plan data copied to the device in one transfer; returns the (provisional) DEVICE address of the copy

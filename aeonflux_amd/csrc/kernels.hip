@@ -15,6 +15,7 @@
 //                       MSM_NAF (batch-constant scalars - the issuer key - as a wave-uniform width-5 NAF schedule) (P1, P4 iii, I1)
 //   k_hash              STROBE-128/merlin transcript over Keccak-f[1600] driven by a precompiled byte
 //                       schedule; squeezes challenges / blinding factors                   (P2, P4 iv-v)
+//   k_mask_rows         zeroes the cells of failed items in the listed output rows (blind issuance), in front of k_finish
 //   k_finish            per-item status byte
 //   k_from_uniform, k_reduce_wide   RistrettoPoint::from_uniform_bytes, Scalar::from_bytes_mod_order_wide
 //   k_sha512            SHA-512 of a byte range of every item's row (sha512.cuh): what turns application data into attributes
@@ -1698,6 +1699,17 @@ __global__ void k_fill_u32(const afx_fill_job* __restrict__ jobs, const afx_row*
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < job.n) job.p[i] = job.v;
 }
+// output masking: one grid row per output row, a lane per item; a failed item's 32-byte cell becomes zeros (two 16-byte stores)
+__global__ void __launch_bounds__(AFX_BLOCK) k_mask_rows(const afx_mask_job* __restrict__ jobs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
+  const afx_mask_job job = *row_job(jobs, rows);
+  const afx_pass pass = passes[row_pass_index(rows)];   // wave-uniform: scalar loads
+  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
+  if (item >= pass.count) return;
+  if (pass.bad[item] == 0) return;
+  uint4* cell = reinterpret_cast<uint4*>(job.p + 32ull * item);
+  cell[0] = make_uint4(0u, 0u, 0u, 0u);
+  cell[1] = make_uint4(0u, 0u, 0u, 0u);
+}
 __global__ void __launch_bounds__(AFX_BLOCK, 2) k_from_uniform(const uint8_t* __restrict__ wide, uint8_t* __restrict__ out_enc, int32_t* out_var, uint32_t count) {
   const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
   if (item >= count) return;
@@ -2082,6 +2094,11 @@ hipError_t afxk_hash(hipStream_t s, const afx_hash_program* progs, uint32_t npro
 }
 hipError_t afxk_finish(hipStream_t s, const afx_finish_job* jobs, uint32_t njobs, const afx_row* rows, uint32_t max_count) {
   hipLaunchKernelGGL(k_finish, dim3((max_count + 255) / 256, njobs), dim3(256), 0, s, jobs, rows);
+  return hipGetLastError();
+}
+hipError_t afxk_mask_rows(hipStream_t s, const afx_mask_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) {
+  if (njobs == 0 || max_count == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_mask_rows, dim3((max_count + 255) / 256, njobs), dim3(256), 0, s, jobs, rows, passes);
   return hipGetLastError();
 }
 hipError_t afxk_fill_u32(hipStream_t s, const afx_fill_job* jobs, uint32_t njobs, const afx_row* rows, uint32_t max_n) {

@@ -111,6 +111,9 @@ typedef struct {
 /* rows of the small utility launches that open and close a plan */
 typedef struct { uint32_t* p; uint32_t v, n; } afx_fill_job;                                            /* p[0..n) = v                */
 typedef struct { const uint32_t* bad; uint8_t* status; uint32_t count, fail_code; } afx_finish_job;     /* status[i] = bad[i] ? code : 0 */
+/* k_mask_rows, one grid row per job, one lane per item: the 32-byte cell of item i in the output row `p` ([count][32], 16-byte aligned) is
+ * zeroed when bad[i] != 0.  Runs in front of k_finish: a failed item's outputs never leave the call (blind issuance). */
+typedef struct { uint8_t* p; } afx_mask_job;
 typedef struct { const uint8_t* wide; uint8_t* out_enc; int32_t* out_var; } afx_uniform_job;            /* RistrettoPoint::from_uniform_bytes */
 typedef struct { const uint8_t* wide; uint8_t* out; } afx_reduce_job;                                   /* Scalar::from_bytes_mod_order_wide  */
 /* k_sha512, one lane per item: out[item] = SHA-512 of the `len` bytes at src + item * stride + offset, 64 bytes (16-byte aligned rows).

@@ -812,6 +812,117 @@ int afx_verify_presentations_batchable_wire(afx_ctx* ctx, const uint8_t* blob, s
 int afx_show_batchable_wire(afx_ctx* ctx, afx_show_group* groups, size_t n_groups, uint8_t* out, size_t out_cap, size_t* out_len,
                             uint8_t* status, size_t status_len);
 
+/* ---- Blind issuance: hidden attributes stay encrypted at the issuer ----------------------------
+ * Issuer::issue reads every attribute in the clear (src/issuer.rs:96-98, "unblinded"); the crate's
+ * CredentialRequestConstructor::append_hidden_scalar / append_hidden_point / append_ciphertext are stubs (src/user.rs:86-128).  These
+ * four calls are the standard blind issuance of MAC_GGM (CMZ'14 section 4; the 2019/1416 paper the crate's labels cite): the user
+ * ElGamal-encrypts the hidden attributes under a one-time key and proves the request well formed, the issuer evaluates the MAC on the
+ * ciphertexts and proves it did so under its published parameters, the user verifies and decrypts V.  The credential (t, U, V) is byte
+ * for byte the one afx_issue makes from the same t_wide, U_wide and attribute values, so afx_show and the verifiers need no change.
+ * Off unless called: nothing above changes.
+ *
+ * Protocol (normative).  G = SystemParameters.G.  H = the positions whose kind is AFX_ATTR_SECRET_SCALAR or AFX_ATTR_SECRET_POINT, in
+ * increasing order, h = |H|, hs = how many of them are scalars.  M_i as in Messages::from_attributes (m_i*G_m[i], or the point M1).
+ * Every proof uses Transcript::new(b"2019/1416 anonymous credential") and zkp's compact proofs, exactly as the statements above.
+ *
+ * 1. Request (user; needs no issuer key).  Per item: the attribute values of all n positions, a one-time scalar d, r_j =
+ *    from_bytes_mod_order_wide(r_wide[j]) per hidden position, rng_seed.  D = d*G, A_j = r_j*G, B_j = r_j*D + M_i for the j-th hidden
+ *    position i, and a proof under the label "2019/1416 blind request proof":
+ *      scalars  "d", then per hidden position "r" and, for a scalar kind, "m" directly after it
+ *      points   "G", "D", then per hidden position "A", "B" and, for a scalar kind, "G_m" (= G_m[i])
+ *      constraints  D = d*G;  per hidden position A = r*G and, for a scalar kind, B = r*D + m*G_m[i]
+ *    A hidden point's B is allocated but not constrained (any pair encrypts some point; A = r*G makes it extractable, allocating B
+ *    binds it into the challenge).  1 + h + hs responses.
+ * 2. Blind issue (issuer).  The request is verified as a zkp Verifier verifies it: canonical scalars, points that decode, no allocated
+ *    point whose encoding is 32 zero bytes, the recomputed challenge equal to the received one.  For an item that passes: t and U from
+ *    t_wide / U_wide exactly as afx_issue draws them, r' = from_bytes_mod_order_wide(rprime_wide),
+ *      V'  = W + x0*U + (x1*t)*U + sum_{i not in H} y_i*M_i
+ *      S1  = r'*G + sum_{i in H} y_i*A_i
+ *      S2  = r'*D + V' + sum_{i in H} y_i*B_i
+ *    and a proof under the label "2019/1416 blind issuance proof":
+ *      scalars  w, w', x_0, x_1, y (n times), "1", "r'"                                   (n + 6 responses)
+ *      points   the issuance proof's own allocations in its order and with its labels, without its V: G_V, G_w, G_w_prime, -G_x_0,
+ *               -G_x_1, every -G_y (all max(3, n)), C_W, I, U, tU; then "G", "D", "S1", "S2"; then per position 0 .. n-1 "A", "B"
+ *               for a hidden position, "M" for a revealed one
+ *      constraints  C_W = w*G_w + w'*G_w';  I = 1*G_V + x_0*(-G_x_0) + x_1*(-G_x_1) + sum_{i<n} y_i*(-G_y_i);
+ *                   S1 = r'*G + sum_H y_i*A_i;  S2 = w*G_w + x_0*U + x_1*tU + r'*D + sum_i y_i*(B_i or M_i)
+ * 3. Unblind (user).  The issuance proof is verified, tU recomputed from t and U; then V = S2 - d*S1.  The credential is (t, U, V) with
+ *    the attributes the user already holds.
+ *
+ * Statuses.  One failure code per call: afx_blind_request AFX_ST_MAC_CREATION (a non-canonical d or scalar value, a point value that
+ * does not decode - all n positions are checked - or a D, A or B that would be the identity encoding); afx_verify_blind_requests,
+ * afx_issue_blind (anything wrong with the item's request or its revealed values) and afx_unblind_issuances (anything wrong with the
+ * issuance, the proof, d or the user's own D, A, B) AFX_ST_VERIFICATION_FAILURE.  Whole shapes: n_attributes != the context's n or a
+ * kind above AFX_ATTR_SECRET_POINT fails every item - AFX_ST_MAC_CREATION from afx_blind_request and afx_issue_blind (amacs.rs:285-287,
+ * as afx_issue), AFX_ST_VERIFICATION_FAILURE from the other two; a wrong response count (n_responses != 1 + h + hs of a request,
+ * != n + 6 of an issuance) fails every item with AFX_ST_VERIFICATION_FAILURE.
+ * AN ITEM THAT FAILS GETS ZEROS IN EVERY OUTPUT ROW OF THE CALL, written on the device (k_mask_rows, in front of k_finish) before
+ * the call completes: the issuer releases no S1, S2 or response for a request whose proof it did not accept.  (A whole-shape failure
+ * of a host-pointer form is answered on the host: the statuses, and zeros in the outputs.)
+ *
+ * Secrets.  d, r_j, m_i and the request proof's blindings; the key, t, r' and the issuance proof's blindings; d again in d*S1: the
+ * plans of afx_blind_request, afx_issue_blind and afx_unblind_issuances are prover-side plans and run under the context's
+ * secret-independent addressing (afx_ctx_set_secret_independent_addressing, mode 2 by default) like afx_issue and afx_show.  The
+ * PUBLIC verification inside afx_issue_blind (the request) and inside afx_unblind_issuances (the issuance proof) SHARES its plan's
+ * secret setting - the flag is not toggled within a plan - so it runs the secret-independent tables too; afx_verify_blind_requests,
+ * which holds no secret, runs the fast ones.  Rows that hold r', x0 + x1*t, y_i*m_i or d*S1 are zeroed on the device, in stream
+ * order, before the call completes.
+ *
+ * Out of scope: wire formats, the group, mixed and coalesced forms, _rng draws, the batchable encoding of the two proofs, the Rust
+ * shim, bench.py.  The host-pointer forms take the context in turn and stage a call in one piece; counts beyond
+ * afx_ctx_set_chunk_items run as several passes.  `_dev`: every pointer a device pointer, rows 16-byte aligned, the call asynchronous
+ * on afx_ctx_stream. */
+/* (declared apart from their typedefs, like afx_device_rng: the Rust shim does not bind them) */
+struct afx_blind_request_randomness {
+  const uint8_t* r_wide;      /* [h][count][64]  one-time encryption randomness per hidden position */
+  const uint8_t* rng_seed;    /* [count][32]     the 32 bytes zkp's prove_compact draws              */
+};
+typedef struct afx_blind_request_randomness afx_blind_request_randomness;
+struct afx_blind_request_soa {  /* written by afx_blind_request, read by the other three */
+  uint8_t* D;                 /* [count] Pt                 */
+  uint8_t* A;                 /* [h][count] Pt              */
+  uint8_t* B;                 /* [h][count] Pt              */
+  uint8_t* challenge;         /* [count] Sc                 */
+  uint8_t* responses;         /* [1 + h + hs][count] Sc     */
+};
+typedef struct afx_blind_request_soa afx_blind_request_soa;
+struct afx_blind_issue_randomness {
+  const uint8_t* t_wide;      /* [count][64]  as afx_issue_randomness */
+  const uint8_t* U_wide;      /* [count][64]                           */
+  const uint8_t* rprime_wide; /* [count][64]  r'                       */
+  const uint8_t* rng_seed;    /* [count][32]                           */
+};
+typedef struct afx_blind_issue_randomness afx_blind_issue_randomness;
+struct afx_blind_issuance_soa { /* written by afx_issue_blind, read by afx_unblind_issuances */
+  uint8_t* t;                 /* [count] Sc            */
+  uint8_t* U;                 /* [count] Pt            */
+  uint8_t* S1;                /* [count] Pt            */
+  uint8_t* S2;                /* [count] Pt            */
+  uint8_t* challenge;         /* [count] Sc            */
+  uint8_t* responses;         /* [n + 6][count] Sc     */
+};
+typedef struct afx_blind_issuance_soa afx_blind_issuance_soa;
+/* attrs->values: [n][count], all positions.  d: [count] Sc.  Any context. */
+int afx_blind_request(afx_ctx* ctx, const afx_attributes_soa* attrs, const uint8_t* d, const afx_blind_request_randomness* rnd, size_t count,
+                      const afx_blind_request_soa* out, uint8_t* status);
+int afx_blind_request_dev(afx_ctx* ctx, const afx_attributes_soa* attrs, const uint8_t* d, const afx_blind_request_randomness* rnd, size_t count,
+                          const afx_blind_request_soa* out, uint8_t* status_dev);
+/* statuses only; attrs->values is not read (may be NULL).  Any context. */
+int afx_verify_blind_requests(afx_ctx* ctx, const afx_attributes_soa* attrs, const afx_blind_request_soa* requests, uint32_t n_responses, size_t count,
+                              uint8_t* status);
+int afx_verify_blind_requests_dev(afx_ctx* ctx, const afx_attributes_soa* attrs, const afx_blind_request_soa* requests, uint32_t n_responses,
+                                  size_t count, uint8_t* status_dev);
+/* needs the issuer key (AFX_E_NO_KEY).  attrs->values: [n][count]; the rows of hidden positions are never read. */
+int afx_issue_blind(afx_ctx* ctx, const afx_attributes_soa* attrs, const afx_blind_request_soa* requests, uint32_t request_n_responses,
+                    const afx_blind_issue_randomness* rnd, size_t count, const afx_blind_issuance_soa* out, uint8_t* status);
+int afx_issue_blind_dev(afx_ctx* ctx, const afx_attributes_soa* attrs, const afx_blind_request_soa* requests, uint32_t request_n_responses,
+                        const afx_blind_issue_randomness* rnd, size_t count, const afx_blind_issuance_soa* out, uint8_t* status_dev);
+/* requests: the user's own (D, A, B are read); attrs->values: the revealed positions' rows are read.  V: [count] Pt.  Any context. */
+int afx_unblind_issuances(afx_ctx* ctx, const afx_attributes_soa* attrs, const uint8_t* d, const afx_blind_request_soa* requests,
+                          const afx_blind_issuance_soa* issuances, uint32_t n_responses, size_t count, uint8_t* V, uint8_t* status);
+int afx_unblind_issuances_dev(afx_ctx* ctx, const afx_attributes_soa* attrs, const uint8_t* d, const afx_blind_request_soa* requests,
+                              const afx_blind_issuance_soa* issuances, uint32_t n_responses, size_t count, uint8_t* V, uint8_t* status_dev);
+
 /* ---- setup helpers (cold path; still GPU arithmetic) ---------------------------------------- */
 
 /* IssuerParameters::generate (src/parameters.rs:349-362) and W = w*G_w (src/amacs.rs:104): given
