@@ -109,6 +109,8 @@ class DeviceRng(C.Structure):
 
 DRAW_T_WIDE, DRAW_U_WIDE, DRAW_ISSUE_SEED, DRAW_Z_WIDE, DRAW_SHOW_SEED = 0, 1, 2, 3, 4
 DRAW_BATCH_WEIGHTS = 64   # the weights of a batchable verification: 16 bytes per commitment (not served by afx_rng_expand)
+# the blind issuer's draws (afx_issue_blind_wire_rng; not served by afx_rng_expand either)
+DRAW_BLIND_T_WIDE, DRAW_BLIND_U_WIDE, DRAW_BLIND_RPRIME_WIDE, DRAW_BLIND_ISSUE_SEED = 65, 66, 67, 68
 
 
 class CommitmentsSoA(C.Structure):
@@ -141,7 +143,7 @@ def DRAW_ENC_SEED(j):
 
 
 def draw_bytes(label):
-    return 64 if label in (DRAW_T_WIDE, DRAW_U_WIDE, DRAW_Z_WIDE) else 32
+    return 64 if label in (DRAW_T_WIDE, DRAW_U_WIDE, DRAW_Z_WIDE, DRAW_BLIND_T_WIDE, DRAW_BLIND_U_WIDE, DRAW_BLIND_RPRIME_WIDE) else 32
 
 
 class CoalescingStats(C.Structure):
@@ -326,6 +328,23 @@ def lib():
                                                      C.c_size_t, C.POINTER(C.c_size_t)]
             _LIB.afx_verify_presentations_batchable_wire.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(DeviceRng), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
             _LIB.afx_show_batchable_wire.argtypes = [C.c_void_p, C.POINTER(ShowGroup), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t]
+        # (the issuer's side of blind issuance on bytes: wire_blind.cpp, likewise left out of the other host-simulation builds)
+        if hasattr(_LIB, "afx_issue_blind_wire"):
+            for fmt in ("request", "issuance"):
+                getattr(_LIB, "afx_blind_%s_wire_header_bytes" % fmt).restype = C.c_size_t
+                getattr(_LIB, "afx_blind_%s_wire_header_bytes" % fmt).argtypes = [C.c_uint32]
+                getattr(_LIB, "afx_blind_%s_wire_parse" % fmt).argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+                getattr(_LIB, "afx_blind_%s_wire_section_bytes" % fmt).argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+            _LIB.afx_blind_request_wire_pack.argtypes = [C.POINTER(AttributesSoA), C.POINTER(BlindRequestSoA), C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+            _LIB.afx_blind_issuance_wire_pack.argtypes = [C.POINTER(AttributesSoA), C.POINTER(BlindIssuanceSoA), C.c_uint32, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                          C.POINTER(C.c_size_t)]
+            for name in ("afx_issue_blind_wire", "afx_group_issue_blind_wire"):
+                getattr(_LIB, name).argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(BlindIssueRandomness), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                                C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+            for name in ("afx_issue_blind_wire_rng", "afx_group_issue_blind_wire_rng"):
+                getattr(_LIB, name).argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(DeviceRng), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                                C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+            _LIB.afx_verify_blind_requests_wire.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         if hasattr(_LIB, "afx_issuer_keygen"):
             _LIB.afx_issuer_keygen.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p]
     return _LIB

@@ -687,7 +687,7 @@ int afx::drain_deferred(afx_ctx* c, afx::Deferred& d) {
   return rc;
 }
 
-int host_pipe(afx_ctx* c, size_t count, const SliceFn& slice, const PlanKey& join_key) {
+int host_pipe(afx_ctx* c, size_t count, const SliceFn& slice, const PlanKey& join_key, bool never_collect) {
   if (c->session && !c->session->paused) {
     // collected: one slice, staged into the session's images; nothing is waited for here
     Stager st(c, c->session->lane, c->session);
@@ -696,7 +696,7 @@ int host_pipe(afx_ctx* c, size_t count, const SliceFn& slice, const PlanKey& joi
   if (c->lock_depth == 1) {
     // the outermost call on this context: a small one joins the other threads' small calls, anything else needs the context to itself
     const afx_ctx::Coalesce& co = c->co;
-    if (co.enabled && co.max_items && count && count <= co.max_call_items && c->small_batch_items && count <= c->small_batch_items && !c->trace &&
+    if (!never_collect && co.enabled && co.max_items && count && count <= co.max_call_items && c->small_batch_items && count <= c->small_batch_items && !c->trace &&
         !c->pipelining && !c->cur_stager)
       return coalesced_call(c, count, slice, join_key);
     // (a group of a mixed request too large to be collected: what the request's small groups left with the sessions goes first -

@@ -525,4 +525,7 @@ inline size_t host_first_slice_items(const afx_ctx* c) { return c->trace ? ~size
 // `join_key` (optional): what makes two calls of this front end the same pass apart from their items - statement, shape, mode, which
 // optional arrays are present.  With it, a small call may run in the coalescer's shared session (afx_ctx::co) and share a pass
 // with other threads' calls of the same key; the front end must then stage per-item data with add_rows() / dev_items() only.
-int host_pipe(afx_ctx* c, size_t count, const std::function<int(Stager&, size_t, size_t)>& slice, const PlanKey& join_key = PlanKey());
+// `never_collect`: the call's plans are not laid out for shared item slots - however small, it is not handed to the coalescer but
+// waits for the context and runs its slices itself.
+int host_pipe(afx_ctx* c, size_t count, const std::function<int(Stager&, size_t, size_t)>& slice, const PlanKey& join_key = PlanKey(),
+              bool never_collect = false);

@@ -397,3 +397,129 @@ def show_batchable_wire(ctx, items):
     check(fn(ctx.h, arr, len(items), out.ctypes.data, out.size, C.byref(out_len), status.ctypes.data, total))
     shapes = [Shape.from_buffer_copy(bytes(arr[g].shape_out)) for g in range(len(items))]
     return out[:out_len.value].tobytes(), shapes, status[:total]
+
+
+# ---- blind issuance on bytes: requests ("AFXQ" v1) in, issuances ("AFXJ" v1) out -------------------
+def _blind_header(magic, kinds, count, cells, n_responses):
+    h = magic + struct.pack("<5I", 1, count, cells, len(kinds), n_responses) + bytes(kinds)
+    return h + bytes(-len(h) % 32)
+
+
+def pack_blind_requests(kinds, values, req):
+    """kinds: AFX_ATTR_* per position; values [n,count,32] (the rows of hidden positions are not read); req: the dict batch.blind_request
+    returns (D, challenge [count,32]; A, B [h,count,32]; responses [1+h+hs,count,32]) -> one AFXQ section"""
+    from .batch import blind_layout
+    n = len(kinds)
+    h, hs = blind_layout(kinds)
+    count = np.asarray(req["D"]).shape[0]
+    u8 = lambda a, rows: np.asarray(a, dtype=np.uint8).reshape(rows, count, 32)
+    cols = [u8(req["D"], 1), u8(req["A"], h), u8(req["B"], h), u8(req["challenge"], 1), u8(req["responses"], 1 + h + hs)]
+    if n > h:
+        values = u8(values, n)
+        cols += [values[i][None] for i in range(n) if kinds[i] not in (1, 4)]
+    soa = np.concatenate(cols, axis=0)
+    cells = 3 + 2 * h + hs + n
+    assert soa.shape == (cells, count, 32)
+    return _blind_header(b"AFXQ", kinds, count, cells, 1 + h + hs) + np.ascontiguousarray(soa.transpose(1, 0, 2)).tobytes()
+
+
+def unpack_blind_requests(blob):
+    """one AFXQ section -> (kinds, values [n,count,32] with zeros in the rows of hidden positions, request dict)"""
+    from .batch import blind_layout
+    assert blob[:4] == b"AFXQ"
+    ver, count, cells, n, nr = struct.unpack("<5I", blob[4:24])
+    kinds = list(blob[24:24 + n])
+    h, hs = blind_layout(kinds)
+    assert ver == 1 and nr == 1 + h + hs and cells == 3 + 2 * h + hs + n
+    o = (24 + n + 31) & ~31
+    assert len(blob) == o + count * cells * 32
+    rec = np.frombuffer(blob, dtype=np.uint8, count=count * cells * 32, offset=o).reshape(count, cells, 32).transpose(1, 0, 2)
+    c = lambda a: np.ascontiguousarray(a)
+    req = {"D": c(rec[0]), "A": c(rec[1:1 + h]), "B": c(rec[1 + h:1 + 2 * h]), "challenge": c(rec[1 + 2 * h]), "responses": c(rec[2 + 2 * h:2 + 2 * h + nr])}
+    values = np.zeros((n, count, 32), np.uint8)
+    at = 2 + 2 * h + nr
+    for i in range(n):
+        if kinds[i] not in (1, 4):
+            values[i] = rec[at]
+            at += 1
+    return kinds, values, req
+
+
+def pack_blind_issuances(kinds, iss):
+    """kinds: the layout the issuances answer; iss: the dict batch.issue_blind returns (t, U, S1, S2, challenge [count,32], responses
+    [nr,count,32]) -> one AFXJ section"""
+    count, nr = np.asarray(iss["t"]).shape[0], np.asarray(iss["responses"]).shape[0]
+    cols = [np.asarray(iss[f], dtype=np.uint8).reshape(1, count, 32) for f in ("t", "U", "S1", "S2", "challenge")]
+    cols.append(np.asarray(iss["responses"], dtype=np.uint8).reshape(nr, count, 32))
+    soa = np.concatenate(cols, axis=0)
+    return _blind_header(b"AFXJ", kinds, count, 5 + nr, nr) + np.ascontiguousarray(soa.transpose(1, 0, 2)).tobytes()
+
+
+def unpack_blind_issuances(blob):
+    """one AFXJ section -> (kinds, the issuance dict batch.unblind_issuances takes)"""
+    assert blob[:4] == b"AFXJ"
+    ver, count, cells, n, nr = struct.unpack("<5I", blob[4:24])
+    assert ver == 1 and cells == 5 + nr
+    kinds = list(blob[24:24 + n])
+    o = (24 + n + 31) & ~31
+    assert len(blob) == o + count * cells * 32
+    rec = np.frombuffer(blob, dtype=np.uint8, count=count * cells * 32, offset=o).reshape(count, cells, 32).transpose(1, 0, 2)
+    c = lambda a: np.ascontiguousarray(a)
+    return kinds, {"t": c(rec[0]), "U": c(rec[1]), "S1": c(rec[2]), "S2": c(rec[3]), "challenge": c(rec[4]), "responses": c(rec[5:5 + nr])}
+
+
+def blind_section_bytes(blob):
+    """the length of the AFXQ or AFXJ section at the start of blob (AfxError if its header is malformed or it runs past the end)"""
+    import ctypes as C
+    from . import check, lib
+    n = C.c_size_t(0)
+    fn = lib().afx_blind_issuance_wire_section_bytes if blob[:4] == b"AFXJ" else lib().afx_blind_request_wire_section_bytes
+    check(fn(blob, len(blob), C.byref(n)))
+    return n.value
+
+
+def issue_blind_wire(ctx, blob, rnd):
+    """afx_issue_blind_wire (afx_group_issue_blind_wire for a Group): a stream of AFXQ sections -> (AFXJ bytes, status per request in
+    stream order).  rnd: dict t_wide, U_wide, rprime_wide [count,64], rng_seed [count,32] in stream order."""
+    import ctypes as C
+    from . import BlindIssueRandomness, check, lib
+    fn = lib().afx_group_issue_blind_wire if hasattr(ctx, "member") else lib().afx_issue_blind_wire
+    out_len, cnt = C.c_size_t(0), C.c_size_t(0)
+    check(fn(ctx.h, blob, len(blob), None, None, 0, C.byref(out_len), None, 0, C.byref(cnt)))
+    names = (("t_wide", 64), ("U_wide", 64), ("rprime_wide", 64), ("rng_seed", 32))
+    arrs = {k: np.ascontiguousarray(rnd[k], dtype=np.uint8) for k, _ in names}
+    for k, w in names:
+        assert arrs[k].size >= cnt.value * w, k
+        if arrs[k].size == 0:          # (an empty stream: the call still refuses a NULL array)
+            arrs[k] = np.zeros(w, np.uint8)
+    r = BlindIssueRandomness(*(arrs[k].ctypes.data for k, _ in names))
+    out = np.zeros(max(1, out_len.value), np.uint8)
+    status = np.full(max(1, cnt.value), 255, np.uint8)
+    check(fn(ctx.h, blob, len(blob), C.byref(r), out.ctypes.data, out.size, C.byref(out_len), status.ctypes.data, status.size, C.byref(cnt)))
+    return out[:out_len.value].tobytes(), status[:cnt.value]
+
+
+def issue_blind_wire_rng(ctx, blob, seed=None, stream=0):
+    """afx_issue_blind_wire_rng (afx_group_issue_blind_wire_rng for a Group): issue_blind_wire with t_wide, U_wide, rprime_wide and
+    rng_seed drawn on the device from (seed, stream) at each request's index in the stream"""
+    import ctypes as C
+    from . import check, lib
+    fn = lib().afx_group_issue_blind_wire_rng if hasattr(ctx, "member") else lib().afx_issue_blind_wire_rng
+    rng = _device_rng(seed, stream)
+    out_len, cnt = C.c_size_t(0), C.c_size_t(0)
+    check(fn(ctx.h, blob, len(blob), C.byref(rng), None, 0, C.byref(out_len), None, 0, C.byref(cnt)))
+    out = np.zeros(max(1, out_len.value), np.uint8)
+    status = np.full(max(1, cnt.value), 255, np.uint8)
+    check(fn(ctx.h, blob, len(blob), C.byref(rng), out.ctypes.data, out.size, C.byref(out_len), status.ctypes.data, status.size, C.byref(cnt)))
+    return out[:out_len.value].tobytes(), status[:cnt.value]
+
+
+def verify_blind_requests_wire(ctx, blob):
+    """afx_verify_blind_requests_wire: the status of every request of a stream of AFXQ sections, in stream order"""
+    import ctypes as C
+    from . import check, lib
+    n = C.c_size_t(0)
+    cap = max(1, len(blob) // 96)   # a record is at least three cells
+    status = np.full(cap, 255, np.uint8)
+    check(lib().afx_verify_blind_requests_wire(ctx.h, blob, len(blob), status.ctypes.data, cap, C.byref(n)))
+    return status[:n.value]

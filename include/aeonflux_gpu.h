@@ -696,7 +696,14 @@ int afx_group_show_wire(afx_group* group, afx_show_group* groups, size_t n_group
 #define AFX_DRAW_Z_WIDE 3u
 #define AFX_DRAW_SHOW_SEED 4u
 #define AFX_DRAW_ENC_SEED(j) (5u + (uint32_t)(j))   /* j < AFX_MAX_ATTRIBUTES */
-#define AFX_DRAW_BYTES(label) (((label) == AFX_DRAW_T_WIDE || (label) == AFX_DRAW_U_WIDE || (label) == AFX_DRAW_Z_WIDE) ? 64u : 32u)
+/* the blind issuer's draws (afx_issue_blind_wire_rng, "Blind issuance on bytes" below): above AFX_DRAW_BATCH_WEIGHTS (64), because
+ * afx_rng_expand keeps serving the labels up to AFX_DRAW_ENC_SEED(31) only */
+#define AFX_DRAW_BLIND_T_WIDE 65u        /* 64 bytes */
+#define AFX_DRAW_BLIND_U_WIDE 66u        /* 64 bytes */
+#define AFX_DRAW_BLIND_RPRIME_WIDE 67u   /* 64 bytes */
+#define AFX_DRAW_BLIND_ISSUE_SEED 68u    /* 32 bytes */
+#define AFX_DRAW_BYTES(label) (((label) == AFX_DRAW_T_WIDE || (label) == AFX_DRAW_U_WIDE || (label) == AFX_DRAW_Z_WIDE || \
+                                ((label) >= AFX_DRAW_BLIND_T_WIDE && (label) <= AFX_DRAW_BLIND_RPRIME_WIDE)) ? 64u : 32u)
 /* (declared apart from its typedef: unlike the batch structs above, the Rust shim does not bind it - it keeps the crate's explicit draws,
  * INTEGRATION.md - and tests/test_integration_layouts.py checks the typedef'd structs against the shim's) */
 struct afx_device_rng {
@@ -868,10 +875,11 @@ int afx_show_batchable_wire(afx_ctx* ctx, afx_show_group* groups, size_t n_group
  * which holds no secret, runs the fast ones.  Rows that hold r', x0 + x1*t, y_i*m_i or d*S1 are zeroed on the device, in stream
  * order, before the call completes.
  *
- * Out of scope: wire formats, the group, mixed and coalesced forms, _rng draws, the batchable encoding of the two proofs, the Rust
- * shim, bench.py.  The host-pointer forms take the context in turn and stage a call in one piece; counts beyond
- * afx_ctx_set_chunk_items run as several passes.  `_dev`: every pointer a device pointer, rows 16-byte aligned, the call asynchronous
- * on afx_ctx_stream. */
+ * Out of scope: the user's doors (afx_blind_request and afx_unblind_issuances on bytes, and their draws), mixed small layouts in one
+ * set of launches, coalescing, the batchable encoding of the two proofs, the Rust shim, bench.py.  The issuer's side on bytes, over
+ * one context or a group and with its randomness drawn on the device, is "Blind issuance on bytes" below.  The host-pointer forms
+ * take the context in turn and stage a call in one piece; counts beyond afx_ctx_set_chunk_items run as several passes.  `_dev`:
+ * every pointer a device pointer, rows 16-byte aligned, the call asynchronous on afx_ctx_stream. */
 /* (declared apart from their typedefs, like afx_device_rng: the Rust shim does not bind them) */
 struct afx_blind_request_randomness {
   const uint8_t* r_wide;      /* [h][count][64]  one-time encryption randomness per hidden position */
@@ -922,6 +930,85 @@ int afx_unblind_issuances(afx_ctx* ctx, const afx_attributes_soa* attrs, const u
                           const afx_blind_issuance_soa* issuances, uint32_t n_responses, size_t count, uint8_t* V, uint8_t* status);
 int afx_unblind_issuances_dev(afx_ctx* ctx, const afx_attributes_soa* attrs, const uint8_t* d, const afx_blind_request_soa* requests,
                               const afx_blind_issuance_soa* issuances, uint32_t n_responses, size_t count, uint8_t* V, uint8_t* status_dev);
+
+/* ---- Blind issuance on bytes: AFXQ requests in, AFXJ issuances out ----------------------------
+ * The issuer's side of the section above with the two doors the plain issuer has (afx_issue_wire, afx_issue_wire_rng): serialized
+ * records, and randomness drawn on the device, over one context or a group.  Off unless called: nothing above changes.  H, h, hs as
+ * above.  Both formats are the engine's own, in the style of AFXR / AFXI (32-byte cells, little-endian header words).
+ *
+ * "AFXQ" version 1: a batch of blind credential requests of one layout.
+ *   header  = "AFXQ" | u32le 1 | u32le count | u32le cells_per_record | u32le n_attributes | u32le n_responses
+ *             | kinds[n_attributes] (u8) | zero padding to a multiple of 32 bytes                -> (24 + n + 31) & ~31 bytes
+ *   record  = D | A[h] | B[h] | challenge | responses[1 + h + hs] | the value of every REVEALED position, in position order
+ *             (Sc for scalar kinds, Pt = M1 for point kinds); hidden positions have no value cell
+ *   cells_per_record = 3 + 2h + hs + n_attributes.
+ * Malformed (AFX_E_BAD_ARGS): a wrong magic or version, n_attributes > AFX_MAX_ATTRIBUTES, a kind above AFX_ATTR_SECRET_POINT,
+ * n_responses != 1 + h + hs of the section's own kinds, a cells_per_record that does not match, a truncated header, header padding
+ * that is not zero, a record area of the wrong length: a section that parses packs to the same bytes.  n_attributes = 0 is well
+ * formed (cells_per_record 3, n_responses 1).
+ *
+ * "AFXJ" version 1: a batch of blind issuances.
+ *   header  = "AFXJ" | u32le 1 | u32le count | u32le cells_per_record | u32le n_attributes | u32le n_responses | kinds[n_attributes]
+ *             | zero padding to a multiple of 32 bytes
+ *   record  = t | U | S1 | S2 | challenge | responses[n_responses]
+ *   cells_per_record = 5 + n_responses.
+ * n_attributes and the kinds echo the request section the AFXJ section answers; n_responses is the issuer context's n + 6, so a
+ * section that answers a request of another n still parses (as in AFXI).  Malformed: as above, with n_responses >
+ * AFX_MAX_ATTRIBUTES + 6 in the place of the response-count rule.  AFXJ carries no attribute values: the user holds them.
+ *
+ * Host only, bytes only, no context; each mirrors the AFXR function of the same role. */
+size_t afx_blind_request_wire_header_bytes(uint32_t n_attributes);    /* 0 if n_attributes > AFX_MAX_ATTRIBUTES */
+int afx_blind_request_wire_parse(const uint8_t* blob, size_t len, uint32_t* n_attributes_out, uint8_t kinds_out[AFX_MAX_ATTRIBUTES],
+                                 uint32_t* n_responses_out, size_t* count_out, size_t* records_offset_out);
+int afx_blind_request_wire_section_bytes(const uint8_t* blob, size_t len, size_t* section_len_out);
+/* attrs: n_attributes, kinds and values [n][count][32] (the value rows of hidden positions are not read); requests: host columns as
+ * afx_blind_request wrote them.  blob == NULL only reports the length needed. */
+int afx_blind_request_wire_pack(const afx_attributes_soa* attrs, const afx_blind_request_soa* requests, size_t count, uint8_t* blob,
+                                size_t blob_cap, size_t* len_out);
+size_t afx_blind_issuance_wire_header_bytes(uint32_t n_attributes);
+int afx_blind_issuance_wire_parse(const uint8_t* blob, size_t len, uint32_t* n_attributes_out, uint8_t kinds_out[AFX_MAX_ATTRIBUTES],
+                                  uint32_t* n_responses_out, size_t* count_out, size_t* records_offset_out);
+int afx_blind_issuance_wire_section_bytes(const uint8_t* blob, size_t len, size_t* section_len_out);
+/* attrs: n_attributes and kinds only (values is not read); issuances: host columns as afx_issue_blind wrote them */
+int afx_blind_issuance_wire_pack(const afx_attributes_soa* attrs, const afx_blind_issuance_soa* issuances, uint32_t n_responses, size_t count,
+                                 uint8_t* blob, size_t blob_cap, size_t* len_out);
+/* afx_issue_blind over a stream of AFXQ sections: request bytes in, AFXJ bytes out, both transpositions on the GPU.
+ *  - blob: AFXQ sections back to back.  Every section is parsed in full before anything runs or is written: a malformed section
+ *    anywhere is AFX_E_BAD_ARGS with out and status untouched.
+ *  - rnd: host arrays in stream order (item i of the stream uses t_wide[i], U_wide[i], rprime_wide[i], rng_seed[i]).
+ *  - out: one AFXJ section per request section, in the same order, with the same count, n_attributes and kinds and n_responses =
+ *    ctx n + 6.  status[i] answers the i-th request of the stream; *count_out = their number.
+ *  - A section whose n_attributes is not the context's, or is 0, is all AFX_ST_MAC_CREATION with zero records (what afx_issue_blind
+ *    answers a layout that does not fit).  An item whose status is not AFX_ST_OK has a record of zeros.  Every other record is byte for
+ *    byte what afx_issue_blind + afx_blind_issuance_wire_pack make of the same inputs, and every status is that column path's.
+ *  - out == NULL: only *out_len and *count_out, from the headers and the context's n; no device work, rnd may be NULL.
+ *  - AFX_E_BAD_ARGS, with nothing written to out or status, for out_cap < *out_len, status_cap < the item count or a NULL randomness
+ *    array; AFX_E_NO_KEY for a context without the issuer key.
+ *  - Sections of one layout (n, kinds) are merged into one batch wherever they stand in the stream; a batch larger than
+ *    afx_ctx_set_chunk_items runs as several slices, so staged memory stays bounded.
+ *  - Like the column forms the call takes the context in turn and is NOT collected with other threads' calls: it stages slice after
+ *    slice on the context's two lanes (host_pipe's lanes, asked never to hand the call, however small, to the collector).  Per
+ *    slice the request records are transposed to struct-of-arrays rows (k_aos_to_soa: D, A, B, challenge and responses in front,
+ *    each revealed value on the row of its attribute position; the rows of hidden positions exist and are never read),
+ *    afx_issue_blind_dev runs on those rows, and k_soa_to_aos writes the AFXJ records: two launches beyond the plan.
+ * The group form splits every merged batch over the members (afx_shard_bounds); a stream of at most afx_ctx_set_small_batch_items
+ * requests goes whole to one member, in turn.  Bytes equal the one-context call's. */
+int afx_issue_blind_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, const afx_blind_issue_randomness* rnd, uint8_t* out, size_t out_cap,
+                         size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out);
+int afx_group_issue_blind_wire(afx_group* group, const uint8_t* blob, size_t len, const afx_blind_issue_randomness* rnd, uint8_t* out,
+                               size_t out_cap, size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out);
+/* afx_verify_blind_requests on each section of the stream, the statuses concatenated; needs no key.  A section of another n is all
+ * AFX_ST_VERIFICATION_FAILURE, as the column call answers it.  The same parsing and error contract; nothing but statuses is written. */
+int afx_verify_blind_requests_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, uint8_t* status, size_t status_cap, size_t* count_out);
+/* The four draws of every request made on the device ("Randomness drawn on the device" above): t_wide, U_wide, rprime_wide and
+ * rng_seed of the request with ordinal i in the stream are draw(seed, stream, i, AFX_DRAW_BLIND_T_WIDE / _U_WIDE / _RPRIME_WIDE /
+ * _ISSUE_SEED).  Specified as an equivalence: the call returns what afx_issue_blind_wire returns when rnd holds those draws, error
+ * codes included.  rng == NULL: AFX_E_BAD_ARGS.  A NULL seed is read from getrandom(2) once per call (a group call: one seed for the
+ * whole group); the library zeroes its copies of the seed as the other *_rng forms do. */
+int afx_issue_blind_wire_rng(afx_ctx* ctx, const uint8_t* blob, size_t len, const afx_device_rng* rng, uint8_t* out, size_t out_cap,
+                             size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out);
+int afx_group_issue_blind_wire_rng(afx_group* group, const uint8_t* blob, size_t len, const afx_device_rng* rng, uint8_t* out,
+                                   size_t out_cap, size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out);
 
 /* ---- setup helpers (cold path; still GPU arithmetic) ---------------------------------------- */
 
