@@ -13,10 +13,8 @@
 #include <memory>
 #include <mutex>
 #include <string>
-#include <system_error>
-#include <thread>
 #include <vector>
-#include "statements.hpp"
+#include "doors.hpp"
 
 // Host threads follow their devices: a member's thread runs on the CPUs of the NUMA node its GPU hangs off (afx::cpus_of_device,
 // plans.cpp), so that the pageable-to-pinned staging copies and the pinned buffers themselves (first touched by that thread) stay
@@ -30,7 +28,7 @@ using afx::cpus_of_device;
 struct afx_group {
   std::vector<afx_ctx*> members;
   std::vector<NodeCpus> node_cpus;   // per member: where its host thread runs
-  std::atomic<uint32_t> next_small{ 0 };   // small calls go to one member each, in turn (run_members)
+  std::atomic<uint32_t> next_small{ 0 };   // small calls go to one member each, in turn (afx_group_pick_small)
   ~afx_group() { for (afx_ctx* m : members) afx_ctx_destroy(m); }   // wipes every member's copy of the key
 };
 
@@ -87,7 +85,23 @@ static MemberSettings settings_of(afx_ctx* c) {
 }
 uint32_t afx_group_small_batch_items(afx_group* g) { return g && !g->members.empty() ? settings_of(g->members[0]).small_batch_items : 0; }
 
-// one host thread per member; the first failure (lowest member index) is reported, with its message
+// Which member takes a call small enough for the latency plan: the next in turn, counted per group - but only while the members are
+// interchangeable: settings are per member (afx_group_member), and a call must not see strict mode, secret-independent addressing,
+// kernel timing or a challenge trace on every m-th call only.  Members that differ (a test set one of them up on purpose): member 0,
+// whose threshold routed the call here, takes every small call.
+uint32_t afx_group_pick_small(afx_group* g) {
+  const uint32_t m = g ? (uint32_t)g->members.size() : 0;
+  if (m < 2) return 0;
+  const MemberSettings s0 = settings_of(g->members[0]);
+  bool alike = !s0.trace;   // (a challenge trace is read back from ONE member's buffer)
+  for (uint32_t k = 1; k < m && alike; k++) {
+    const MemberSettings sk = settings_of(g->members[k]);
+    alike = s0.same_as(sk) && !sk.trace;
+  }
+  return alike ? g->next_small.fetch_add(1, std::memory_order_relaxed) % m : 0;
+}
+
+// one host thread per member (doors.hpp on_members); the first failure (lowest member index) is reported, with its message
 template <class F>
 static int run_members(afx_group* g, size_t count, F&& call) {
   const uint32_t m = (uint32_t)g->members.size();
@@ -95,43 +109,18 @@ static int run_members(afx_group* g, size_t count, F&& call) {
   // chain either way) and would pay a host thread per member: it goes to ONE member, the next in turn, so that small calls
   // arriving from several host threads spread over the group's devices (where each member collects the calls it is dealt:
   // afx_ctx_set_coalescing).
-  const MemberSettings s0 = settings_of(g->members[0]);
-  if (m > 1 && count != 0 && count <= s0.small_batch_items) {
-    // ... in turn only while the members are interchangeable: settings are per member (afx_group_member), and a call must not
-    // see strict mode, secret-independent addressing, kernel timing or a challenge trace on every m-th call only.  Members that
-    // differ (a test set one of them up on purpose): member 0, whose threshold routed the call here, takes every small call.
-    bool alike = !s0.trace;   // (a challenge trace is read back from ONE member's buffer)
-    for (uint32_t k = 1; k < m && alike; k++) {
-      const MemberSettings sk = settings_of(g->members[k]);
-      alike = s0.same_as(sk) && !sk.trace;
-    }
-    const uint32_t i = alike ? g->next_small.fetch_add(1, std::memory_order_relaxed) % m : 0;
+  if (m > 1 && count != 0 && count <= afx_group_small_batch_items(g)) {
+    const uint32_t i = afx_group_pick_small(g);
     PinScope pin(g->node_cpus[i], true);
     const int rc = call(g->members[i], (size_t)0, count);
     if (rc) { const std::string why = afx_last_error(); set_error("member " + std::to_string(i) + ": " + why); }
     return rc;
   }
-  std::vector<int> rcs(m, AFX_OK);
-  std::vector<std::string> errs(m);
-  std::vector<std::thread> threads;
-  auto body = [&](uint32_t i) {
+  return on_members(g, m, [&](afx_ctx* c, uint32_t i) -> int {
     size_t first = 0, n = 0;
     afx_shard_bounds(count, m, i, &first, &n);
-    if (n == 0) return;
-    PinScope pin(g->node_cpus[i], i == 0);   // member 0 runs on the caller's thread, which gets its mask back
-    rcs[i] = call(g->members[i], first, n);
-    if (rcs[i]) errs[i] = afx_last_error();   // the error string is per thread
-  };
-  // a member whose thread cannot be started runs on this one; the members' calls themselves do not throw (C entry points)
-  threads.reserve(m);
-  for (uint32_t i = 1; i < m; i++) {
-    try { threads.emplace_back(body, i); } catch (const std::system_error&) { body(i); }
-  }
-  body(0);
-  for (std::thread& t : threads) t.join();
-  for (uint32_t i = 0; i < m; i++)
-    if (rcs[i]) { set_error("member " + std::to_string(i) + ": " + errs[i]); return rcs[i]; }
-  return AFX_OK;
+    return n ? call(c, first, n) : AFX_OK;
+  });
 }
 
 extern "C" int afx_group_verify_presentations(afx_group* g, const afx_shape* shape, const afx_presentation_soa* batch, size_t count, uint8_t* status) try {

@@ -6,23 +6,14 @@
 #include <map>
 #include <memory>
 #include <string>
-#include <system_error>
-#include <thread>
 #include <vector>
-#include "statements.hpp"
+#include "doors.hpp"
 
 namespace {
 
 std::string shape_key(const afx_shape& sh) {
   const afx_shape c = canonical_shape(sh);
   return std::string((const char*)&c, sizeof c);
-}
-uint32_t rd32(const uint8_t* b) { return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24); }
-
-// does a request of several groups on this context leave its small groups with the collector's sessions (plans.cpp)?
-bool joins_the_collector(afx_ctx* ctx) {
-  CtxLock probe(ctx, true);
-  return ctx->lock_depth == 1 && ctx->co.enabled && ctx->co.max_items && ctx->small_batch_items && !ctx->trace && !ctx->pipelining && !ctx->session;
 }
 
 // positions given: each < status_len and used once over all groups; not given: contiguous after the groups before
@@ -170,21 +161,8 @@ int run_groups_on_devices(afx_group* group, G* groups, size_t n_groups, uint8_t*
     }
     next += grp.count;
   }
-  std::vector<int> rcs(m, AFX_OK);
-  std::vector<std::string> errs(m);
-  auto body = [&](uint32_t k) {
-    if (share[k].empty()) return;
-    GroupPin pin(group, k, k == 0);   // the member's thread on its device's NUMA node (member 0: the caller's thread, restored)
-    rcs[k] = mixed_on_ctx(afx_group_member(group, k), share[k].data(), share[k].size());
-    if (rcs[k]) errs[k] = afx_last_error();   // the error string is per thread
-  };
-  std::vector<std::thread> threads;
-  for (uint32_t k = 1; k < m; k++) {
-    if (share[k].empty()) continue;
-    try { threads.emplace_back(body, k); } catch (const std::system_error&) { body(k); }
-  }
-  body(0);
-  for (std::thread& t : threads) t.join();
+  // (a member without a share has nothing to do)
+  rc = on_members(group, m, [&](afx_ctx* c, uint32_t k) -> int { return share[k].empty() ? AFX_OK : mixed_on_ctx(c, share[k].data(), share[k].size()); });
   // shape_out and the like were written into the shares' copies of the group structs: hand them back
   {
     std::vector<size_t> at(m, 0);
@@ -197,9 +175,7 @@ int run_groups_on_devices(afx_group* group, G* groups, size_t n_groups, uint8_t*
       groups[g].positions = keep;
     }
   }
-  for (uint32_t k = 0; k < m; k++)
-    if (rcs[k]) { set_error("member " + std::to_string(k) + ": " + errs[k]); return rcs[k]; }
-  return AFX_OK;
+  return rc;
 }
 
 }  // namespace
@@ -473,27 +449,15 @@ extern "C" int afx_group_verify_presentations_mixed_wire(afx_group* group, const
     }
     if (rc) return rc;
   }
-  std::vector<int> rcs(m, AFX_OK);
-  std::vector<std::string> errs(m);
-  auto body = [&](uint32_t k) {
+  return on_members(group, m, [&](afx_ctx* c, uint32_t k) -> int {
     Share& S = share[k];
-    if (S.bytes.empty()) return;
-    GroupPin pin(group, k, k == 0);   // the member's thread on its device's NUMA node (member 0: the caller's thread, restored)
+    if (S.bytes.empty()) return AFX_OK;
     std::vector<uint8_t> mine(S.items, AFX_ST_VERIFICATION_FAILURE);
     size_t got = 0;
-    rcs[k] = afx_verify_presentations_mixed_wire(afx_group_member(group, k), S.bytes.data(), S.bytes.size(), mine.data(), mine.size(), &got);
-    if (rcs[k]) { errs[k] = afx_last_error(); return; }   // the error string is per thread
-    size_t r = 0;
-    for (const auto& rg : S.ranges) { memcpy(status + rg.first, mine.data() + r, rg.second); r += rg.second; }
-  };
-  std::vector<std::thread> threads;
-  for (uint32_t k = 1; k < m; k++) {
-    if (share[k].bytes.empty()) continue;
-    try { threads.emplace_back(body, k); } catch (const std::system_error&) { body(k); }
-  }
-  body(0);
-  for (std::thread& t : threads) t.join();
-  for (uint32_t k = 0; k < m; k++)
-    if (rcs[k]) { set_error("member " + std::to_string(k) + ": " + errs[k]); return rcs[k]; }
-  return AFX_OK;
+    const int r = afx_verify_presentations_mixed_wire(c, S.bytes.data(), S.bytes.size(), mine.data(), mine.size(), &got);
+    if (r) return r;
+    size_t at = 0;
+    for (const auto& rg : S.ranges) { memcpy(status + rg.first, mine.data() + at, rg.second); at += rg.second; }
+    return AFX_OK;
+  });
 } catch (...) { return afx::exception_rc(); }

@@ -15,7 +15,7 @@
 #include <vector>
 #include "engine.hpp"
 #include <stdlib.h>
-#include "statements.hpp"
+#include "doors.hpp"
 
 using namespace afx;
 
@@ -28,7 +28,6 @@ static bool host_scalar_is_canonical(const uint8_t* s) {
   }
   return false;
 }
-static uint32_t rd32(const uint8_t* b) { return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24); }
 static size_t sizeof_system_parameters(uint32_t n) { return n < 3 ? 32 * (5 + 3 + (size_t)n + 4) + 4 : 32 * (5 + 2 * (size_t)n + 4) + 4; }  // parameters.rs:34-40
 static size_t sizeof_secret_key(uint32_t n) { return 32 * (5 + (size_t)n) + 4; }                                                           // amacs.rs:44-46
 

@@ -2,11 +2,7 @@
 // a prover call returns.  Bytes only - the reference defines no serialisation for these messages
 // (/root/reference/src/nizk/presentation.rs:117-127, src/issuer.rs:42-45).
 #include <string.h>
-#include "statements.hpp"
-
-namespace {
-void wr32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
-}
+#include "doors.hpp"
 
 extern "C" int afx_wire_pack_presentations(const afx_shape* shape, const afx_presentation_soa* batch, size_t count, uint8_t* blob, size_t blob_cap,
                                            size_t* len_out) try {

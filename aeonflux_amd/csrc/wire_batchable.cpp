@@ -5,11 +5,9 @@
 // context in turn: the groups of a request run one after the other, none is collected with other threads' calls.
 #include <string.h>
 #include <map>
-#include "statements.hpp"
+#include "doors.hpp"
 
 namespace {
-uint32_t rd32(const uint8_t* b) { return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24); }
-void wr32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
 bool shape_ok(const afx_shape& sh) {
   if (sh.n_attributes > AFX_MAX_ATTRIBUTES || sh.n_responses > 3 + AFX_MAX_ATTRIBUTES || sh.n_hidden_scalars > AFX_MAX_ATTRIBUTES || sh.n_enc_proofs > AFX_MAX_ATTRIBUTES)
     return false;

@@ -5,119 +5,15 @@
 //  - AnonymousCredential::show (src/credential.rs:37-46) straight into AFXP sections: afx_show_dev writes its outputs into the rows of
 //    one scratch region per pass, the revealed attribute values are read from the credential's own value rows, and k_soa_to_aos turns
 //    the region into AFXP records - zeros for an item that failed - which come back in one fetch.
-// Only bytes move on the host.  The scheduling is afx_issue_wire's (wire_issue.cpp): small batches share one set of launches, small
+// Only bytes move on the host.  The scheduling is afx_issue_wire's (doors.hpp run_batches, on_members): small batches share one set of launches, small
 // calls are collected with other threads' calls, large ones go through the two lanes in slices, and a group splits every batch.
-#include <atomic>
 #include <map>
-#include <memory>
 #include <string>
-#include <system_error>
-#include <thread>
 #include <vector>
 #include "kernels.h"
-#include "statements.hpp"
+#include "doors.hpp"
 
 namespace {
-
-uint32_t rd32(const uint8_t* b) { return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24); }
-void wr32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
-
-// does a request of several batches on this context leave its small batches with the collector's sessions (plans.cpp; as mixed.cpp)?
-bool joins_the_collector(afx_ctx* ctx) {
-  CtxLock probe(ctx, true);
-  return ctx->lock_depth == 1 && ctx->co.enabled && ctx->co.max_items && ctx->small_batch_items && !ctx->trace && !ctx->pipelining && !ctx->session;
-}
-
-// Every batch of a request on one context, as wire_issue.cpp run_batches runs them: `run(b)` does batch b whole; counts[b] == 0: nothing
-// to launch.  With the collector on, the small batches join the collecting session; otherwise they are assembled into ONE set of
-// launches of the request's own; a large batch runs by itself, in between.
-template <class Run>
-int run_batches(afx_ctx* ctx, const std::vector<size_t>& counts, Run&& run) {
-  size_t live = 0, only = 0;
-  for (size_t b = 0; b < counts.size(); b++)
-    if (counts[b]) { live++; only = b; }
-  if (live == 0) return AFX_OK;
-  if (live == 1) return run(only);
-  int rc = AFX_OK;
-  afx::Deferred deferred;
-  std::unique_ptr<afx::DeferScope> defer;
-  std::unique_ptr<CtxLock> lock;
-  std::unique_ptr<afx::Session> ses;
-  const bool join = joins_the_collector(ctx);
-  if (join) defer.reset(new afx::DeferScope(&deferred));
-  else lock.reset(new CtxLock(ctx));   // the session owns the context until its last flush
-  if (lock && ctx->small_batch_items && !ctx->trace && !ctx->session) {
-    ses.reset(new afx::Session(ctx));
-    if ((rc = ses->ensure_images(0, 0))) return rc;
-    uint64_t width = 0;   // as in mixed.cpp run_groups
-    for (size_t cnt : counts)
-      if (cnt && cnt <= ctx->small_batch_items) width += (cnt + 63) / 64;
-    ctx->merge_class = afx_ctx::merge_class_of(width);
-  }
-  struct WidthReset { afx_ctx* c; ~WidthReset() { if (c) c->merge_class = 0; } } width_reset = { ses ? ctx : nullptr };
-  try {   // (an exception must not pass the drain below: other threads' calls may sit in a session only this thread launches)
-    for (size_t b = 0; b < counts.size() && !rc; b++) {
-      if (!counts[b]) continue;
-      const bool collect = ses && counts[b] <= ctx->small_batch_items;
-      if (ses && !collect) {
-        if ((rc = ses->flush())) break;
-        ses->paused = true;
-      }
-      rc = run(b);
-      if (ses) ses->paused = false;
-      if (rc) set_error("batch " + std::to_string(b) + ": " + afx_last_error());
-    }
-  } catch (...) {
-    if (!join) throw;
-    rc = afx::exception_rc();
-  }
-  if (ses) {
-    if (rc) ses->drop();
-    else rc = ses->flush();
-    ses.reset();
-  }
-  if (join) {
-    CtxLock lk(ctx, true);
-    const int rc2 = afx::drain_deferred(ctx, deferred);   // (also after a failure: the staged rows point into this request's buffers)
-    if (!rc) rc = rc2;
-    defer.reset();
-  }
-  return rc;
-}
-
-// may small calls of a group go to any member (the members' settings alike, as group.cpp run_members requires)?
-bool members_alike(afx_group* g, uint32_t m) {
-  struct Set { uint32_t sb, chunk; bool strict, fixed, timing, trace; int secret; };
-  auto of = [](afx_ctx* c) { std::lock_guard<std::mutex> l(c->settings_mu); return Set{ c->small_batch_items, c->chunk_items, c->strict, c->fixed_key_schedule, c->timing, c->trace != nullptr, c->secret_mode }; };
-  const Set s0 = of(afx_group_member(g, 0));
-  if (s0.trace) return false;
-  for (uint32_t k = 1; k < m; k++) {
-    const Set s = of(afx_group_member(g, k));
-    if (s.sb != s0.sb || s.chunk != s0.chunk || s.strict != s0.strict || s.fixed != s0.fixed || s.timing != s0.timing || s.secret != s0.secret || s.trace) return false;
-  }
-  return true;
-}
-std::atomic<uint32_t> g_next_small{ 0 };
-
-// Runs body(k) for every member k of `group` on a thread of its own (member 0: the caller's thread); the first failure is returned.
-template <class Body>
-int on_members(afx_group* group, uint32_t m, Body&& body) {
-  std::vector<int> rcs(m, AFX_OK);
-  std::vector<std::string> errs(m);
-  auto one = [&](uint32_t k) {
-    GroupPin pin(group, k, k == 0);   // the member's thread on its device's NUMA node (member 0: the caller's thread, restored)
-    if ((rcs[k] = body(afx_group_member(group, k), k))) errs[k] = afx_last_error();   // (the error string is per thread)
-  };
-  std::vector<std::thread> threads;
-  for (uint32_t k = 1; k < m; k++) {
-    try { threads.emplace_back(one, k); } catch (const std::system_error&) { one(k); }
-  }
-  one(0);
-  for (std::thread& t : threads) t.join();
-  for (uint32_t k = 0; k < m; k++)
-    if (rcs[k]) { set_error("member " + std::to_string(k) + ": " + errs[k]); return rcs[k]; }
-  return AFX_OK;
-}
 
 // ---- CredentialIssuance::verify over AFXI streams -------------------------------------------------------------------------------
 
@@ -493,17 +389,25 @@ extern "C" int afx_issuance_wire_section_bytes(const uint8_t* blob, size_t len, 
   return AFX_OK;
 } catch (...) { return afx::exception_rc(); }
 
-extern "C" int afx_verify_issuances_mixed_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, uint8_t* status, size_t status_cap, size_t* count_out) try {
-  if (!ctx || !count_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  IStream S;
-  int rc = parse_issuances(blob, len, ctx->n, S);
+namespace {
+// a parsed stream (parse_issuances with this context's n) on one context
+int verify_stream(afx_ctx* ctx, IStream& S, const uint8_t* blob, uint8_t* status, size_t status_cap) {
+  int rc = check_issuances(S, status, status_cap);
   if (rc) return rc;
-  *count_out = S.total;
-  if ((rc = check_issuances(S, status, status_cap))) return rc;
   prepare_issuances(S, blob, status);
   if ((rc = run_batches(ctx, launch_counts(S), [&](size_t b) { return verify_records(ctx, S.batches[b], 0, S.batches[b].count); }))) return rc;
   scatter_issuances(S, status);
   return AFX_OK;
+}
+}  // namespace
+
+extern "C" int afx_verify_issuances_mixed_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, uint8_t* status, size_t status_cap, size_t* count_out) try {
+  if (!ctx || !count_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  IStream S;
+  const int rc = parse_issuances(blob, len, ctx->n, S);
+  if (rc) return rc;
+  *count_out = S.total;
+  return verify_stream(ctx, S, blob, status, status_cap);
 } catch (...) { return afx::exception_rc(); }
 
 // The same stream over a group's devices.  A stream of at most afx_ctx_set_small_batch_items issuances (member 0's) goes whole to ONE
@@ -515,14 +419,14 @@ extern "C" int afx_group_verify_issuances_mixed_wire(afx_group* group, const uin
   if (m == 0) { set_error("empty group"); return AFX_E_BAD_ARGS; }
   afx_ctx* c0 = afx_group_member(group, 0);
   const uint32_t small = afx_group_small_batch_items(group);
-  IStream S;
+  IStream S;   // parsed once, for whichever path (the members share the parameters, so member 0's n is every member's)
   int rc = parse_issuances(blob, len, c0->n, S);
   if (rc) return rc;
   *count_out = S.total;
   if (m == 1 || (small && S.total <= small)) {
-    const uint32_t k = m == 1 ? 0 : members_alike(group, m) ? g_next_small.fetch_add(1, std::memory_order_relaxed) % m : 0;
+    const uint32_t k = afx_group_pick_small(group);
     GroupPin pin(group, k, true);
-    rc = afx_verify_issuances_mixed_wire(afx_group_member(group, k), blob, len, status, status_cap, count_out);
+    rc = verify_stream(afx_group_member(group, k), S, blob, status, status_cap);
     if (rc && m > 1) { const std::string why = afx_last_error(); set_error("member " + std::to_string(k) + ": " + why); }
     return rc;
   }
@@ -609,7 +513,7 @@ int group_show_wire(afx_group* group, afx_show_group* groups, size_t n_groups, c
   int rc = plan_show(c0, groups, n_groups, out != nullptr, P, seed40 != nullptr);
   if (rc) return rc;
   if (!out || m == 1 || (small && P.items <= small)) {
-    const uint32_t k = (!out || m == 1) ? 0 : members_alike(group, m) ? g_next_small.fetch_add(1, std::memory_order_relaxed) % m : 0;
+    const uint32_t k = out ? afx_group_pick_small(group) : 0;
     GroupPin pin(group, k, true);
     rc = show_wire(afx_group_member(group, k), groups, n_groups, seed40, out, out_cap, out_len, status, status_len);
     if (rc && m > 1) { const std::string why = afx_last_error(); set_error("member " + std::to_string(k) + ": " + why); }
