@@ -111,6 +111,12 @@ DRAW_T_WIDE, DRAW_U_WIDE, DRAW_ISSUE_SEED, DRAW_Z_WIDE, DRAW_SHOW_SEED = 0, 1, 2
 DRAW_BATCH_WEIGHTS = 64   # the weights of a batchable verification: 16 bytes per commitment (not served by afx_rng_expand)
 # the blind issuer's draws (afx_issue_blind_wire_rng; not served by afx_rng_expand either)
 DRAW_BLIND_T_WIDE, DRAW_BLIND_U_WIDE, DRAW_BLIND_RPRIME_WIDE, DRAW_BLIND_ISSUE_SEED = 65, 66, 67, 68
+# the blind user's draws (afx_blind_request_wire_rng, afx_unblind_issuances_wire_rng)
+DRAW_BLINDREQ_D_WIDE, DRAW_BLINDREQ_SEED = 69, 70
+
+
+def DRAW_BLINDREQ_R_WIDE(j):
+    return 71 + j
 
 
 class CommitmentsSoA(C.Structure):
@@ -138,11 +144,23 @@ class BlindIssuanceSoA(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("t", "U", "S1", "S2", "challenge", "responses")]
 
 
+class BlindRequestGroup(C.Structure):
+    """afx_blind_request_group: the attributes of one layout in afx_blind_request_wire, with d and the request's randomness"""
+    _fields_ = [("attrs", AttributesSoA), ("d", C.c_void_p), ("rnd", BlindRequestRandomness), ("count", C.c_size_t)]
+
+
+class CredentialOut(C.Structure):
+    """afx_credential_out: t, U, V [total] each, where afx_unblind_issuances_wire writes the credentials"""
+    _fields_ = [(k, C.c_void_p) for k in ("t", "U", "V")]
+
+
 def DRAW_ENC_SEED(j):
     return 5 + j
 
 
 def draw_bytes(label):
+    if label == DRAW_BLINDREQ_D_WIDE or DRAW_BLINDREQ_R_WIDE(0) <= label <= DRAW_BLINDREQ_R_WIDE(MAX_ATTRIBUTES - 1):
+        return 64
     return 64 if label in (DRAW_T_WIDE, DRAW_U_WIDE, DRAW_Z_WIDE, DRAW_BLIND_T_WIDE, DRAW_BLIND_U_WIDE, DRAW_BLIND_RPRIME_WIDE) else 32
 
 
@@ -345,6 +363,19 @@ def lib():
                 getattr(_LIB, name).argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(DeviceRng), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                                 C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
             _LIB.afx_verify_blind_requests_wire.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        # (the user's doors of blind issuance on bytes: wire_blind_user.cpp)
+        if hasattr(_LIB, "afx_blind_request_wire"):
+            tail = [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]   # out, out_cap, out_len, status, status_cap, count_out
+            for name in ("afx_blind_request_wire", "afx_group_blind_request_wire"):
+                getattr(_LIB, name).argtypes = [C.c_void_p, C.POINTER(BlindRequestGroup), C.c_size_t] + tail
+            for name in ("afx_blind_request_wire_rng", "afx_group_blind_request_wire_rng"):
+                getattr(_LIB, name).argtypes = [C.c_void_p, C.POINTER(BlindRequestGroup), C.c_size_t, C.POINTER(DeviceRng), C.c_void_p] + tail
+            for name in ("afx_unblind_issuances_wire", "afx_group_unblind_issuances_wire"):
+                getattr(_LIB, name).argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(CredentialOut), C.c_void_p, C.c_size_t,
+                                                C.POINTER(C.c_size_t)]
+            for name in ("afx_unblind_issuances_wire_rng", "afx_group_unblind_issuances_wire_rng"):
+                getattr(_LIB, name).argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(DeviceRng), C.POINTER(CredentialOut), C.c_void_p,
+                                                C.c_size_t, C.POINTER(C.c_size_t)]
         if hasattr(_LIB, "afx_issuer_keygen"):
             _LIB.afx_issuer_keygen.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p]
     return _LIB

@@ -105,4 +105,28 @@ int on_members(afx_group* group, uint32_t m, Body&& body) {
   return AFX_OK;
 }
 
+// The two ways a door's batches go over a group's members, shared by every group door (request_stream.hpp group_door, wire_blind_user.cpp).
+// A small stream whole on ONE member, the next in turn (afx_group_pick_small), the calling thread on that member's NUMA node; the
+// error of a group of several names the member.
+template <class Body>
+int on_one_member(afx_group* group, uint32_t m, Body&& body) {
+  const uint32_t k = afx_group_pick_small(group);
+  GroupPin pin(group, k, true);
+  const int rc = body(afx_group_member(group, k));
+  if (rc && m > 1) { const std::string why = afx_last_error(); set_error("member " + std::to_string(k) + ": " + why); }
+  return rc;
+}
+// Every batch b of counts[b] items split over the members (afx_shard_bounds), one host thread per member: run(member, b, first, n)
+template <class Run>
+int shard_over_members(afx_group* group, uint32_t m, const std::vector<size_t>& counts, Run&& run) {
+  return on_members(group, m, [&](afx_ctx* c, uint32_t k) -> int {
+    for (size_t b = 0; b < counts.size(); b++) {
+      size_t first = 0, n = 0;
+      afx_shard_bounds(counts[b], m, k, &first, &n);
+      if (n) { const int r = run(c, b, first, n); if (r) return r; }
+    }
+    return AFX_OK;
+  });
+}
+
 }  // namespace

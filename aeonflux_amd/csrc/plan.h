@@ -126,9 +126,10 @@ typedef struct { const uint8_t* msgs; uint8_t* M1; uint32_t* counters; uint8_t* 
 /* k_draw, one grid row per job: item i of the row gets draw(seed, stream, index + i, label) (keccak.cuh shake256_draw), AFX_DRAW_LEN(label)
  * bytes at dst + i * AFX_DRAW_LEN(label).  `seed`: the call's 40 staged bytes seed || u64le(stream), 8-byte aligned; dst 16-byte aligned. */
 typedef struct { const uint8_t* seed; uint8_t* dst; uint64_t index; uint32_t count, label; } afx_draw_job;
-/* bytes of one draw: t_wide, U_wide and z_wide and the blind issuer's t_wide, U_wide and rprime_wide (65 to 67) are 64
- * (include/aeonflux_gpu.h AFX_DRAW_*), the seeds 32 */
-#define AFX_DRAW_LEN(label) (((label) == 0u || (label) == 1u || (label) == 3u || ((label) >= 65u && (label) <= 67u)) ? 64u : 32u)
+/* bytes of one draw: t_wide, U_wide and z_wide, the blind issuer's t_wide, U_wide and rprime_wide (65 to 67) and the blind user's
+ * d_wide (69) and r_wide[j] (71 to 102) are 64 (include/aeonflux_gpu.h AFX_DRAW_*), the seeds 32 */
+#define AFX_DRAW_LEN(label) (((label) == 0u || (label) == 1u || (label) == 3u || ((label) >= 65u && (label) <= 67u) || (label) == 69u || \
+                              ((label) >= 71u && (label) <= 102u)) ? 64u : 32u)
 
 /* k_coef (batchable presentation proofs, include/aeonflux_gpu.h): the scalars of the ONE weighted sum that checks every constraint
  * of a presentation's proofs.  One job = one output scalar array (the coefficient of one base of the sum), one grid row per job, one

@@ -267,25 +267,16 @@ inline int group_door(afx_group* group, const Door& d, const uint8_t* blob, size
   int rc = parse_stream(d, blob, len, c0->n, S);
   if (rc) return rc;
   if (m == 1 || (small && len && S.total <= small)) {
-    const uint32_t k = afx_group_pick_small(group);
-    GroupPin pin(group, k, true);
-    rc = run_door(afx_group_member(group, k), d, S, blob, seed40, out, out_cap, out_len, status, status_cap, count_out);
-    if (rc && m > 1) { const std::string why = afx_last_error(); set_error("member " + std::to_string(k) + ": " + why); }
-    return rc;
+    return on_one_member(group, m, [&](afx_ctx* c) { return run_door(c, d, S, blob, seed40, out, out_cap, out_len, status, status_cap, count_out); });
   }
   *out_len = S.out_len;
   *count_out = S.total;
   if (!out) return AFX_OK;
   if ((rc = check_call(c0, d, S, seed40, out_cap, status, status_cap))) return rc;
   prepare(S, d, blob, seed40, c0->n, out, status);
-  rc = on_members(group, m, [&](afx_ctx* c, uint32_t k) -> int {
-    for (const Batch& B : S.batches) {
-      size_t first = 0, n = 0;
-      afx_shard_bounds(B.count, m, k, &first, &n);
-      if (n) { const int r = d.run(c, B, first, n); if (r) return r; }
-    }
-    return AFX_OK;
-  });
+  std::vector<size_t> counts;
+  for (const Batch& B : S.batches) counts.push_back(B.count);
+  rc = shard_over_members(group, m, counts, [&](afx_ctx* c, size_t b, size_t first, size_t n) { return d.run(c, S.batches[b], first, n); });
   scatter(S, d, c0->n, out, status);
   return rc;
 }

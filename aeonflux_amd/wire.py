@@ -523,3 +523,97 @@ def verify_blind_requests_wire(ctx, blob):
     status = np.full(cap, 255, np.uint8)
     check(lib().afx_verify_blind_requests_wire(ctx.h, blob, len(blob), status.ctypes.data, cap, C.byref(n)))
     return status[:n.value]
+
+
+# ---- blind issuance on bytes, the user's doors: columns -> AFXQ, AFXJ -> t, U, V ---------------------
+def _blind_request_groups(groups, explicit):
+    """groups: dicts kinds, values [n,count,32] and, for the explicit door, d [count,32], r_wide [h,count,64], rng_seed [count,32]
+    -> (afx_blind_request_group array, the arrays it points into)"""
+    from . import BlindRequestGroup, BlindRequestRandomness
+    from .batch import _blind_attrs, _hptr
+    u8 = lambda a: np.ascontiguousarray(a, dtype=np.uint8)
+    arr = (BlindRequestGroup * max(1, len(groups)))()
+    keep = []
+    for g, it in enumerate(groups):
+        values = u8(it["values"])
+        arr[g].attrs = _blind_attrs(list(it["kinds"]), values, _hptr)
+        arr[g].count = int(it["count"]) if "count" in it else values.shape[1]
+        keep.append(values)
+        if explicit:
+            d, r_wide, rng_seed = u8(it["d"]), u8(it["r_wide"]), u8(it["rng_seed"])
+            arr[g].d = _hptr(d)
+            arr[g].rnd = BlindRequestRandomness(_hptr(r_wide), _hptr(rng_seed))
+            keep += [d, r_wide, rng_seed]
+    return arr, keep
+
+
+def blind_request_wire(ctx, groups):
+    """afx_blind_request_wire (afx_group_blind_request_wire for a Group): afx_blind_request over groups of columns -> (one AFXQ section
+    per group, back to back; status per item in stream order).  groups: dicts kinds, values [n,count,32], d [count,32], r_wide
+    [h,count,64], rng_seed [count,32]."""
+    import ctypes as C
+    from . import check, lib
+    fn = lib().afx_group_blind_request_wire if hasattr(ctx, "member") else lib().afx_blind_request_wire
+    arr, keep = _blind_request_groups(groups, True)
+    out_len, cnt = C.c_size_t(0), C.c_size_t(0)
+    check(fn(ctx.h, arr, len(groups), None, 0, C.byref(out_len), None, 0, C.byref(cnt)))
+    out = np.zeros(max(1, out_len.value), np.uint8)
+    status = np.full(max(1, cnt.value), 255, np.uint8)
+    check(fn(ctx.h, arr, len(groups), out.ctypes.data, out.size, C.byref(out_len), status.ctypes.data, status.size, C.byref(cnt)))
+    return out[:out_len.value].tobytes(), status[:cnt.value]
+
+
+def blind_request_wire_rng(ctx, groups, seed=None, stream=0, keep_d=True):
+    """afx_blind_request_wire_rng (its group form for a Group): blind_request_wire with d, r_wide and rng_seed drawn on the device from
+    (seed, stream) at each item's index in the stream; groups need kinds and values only.  Returns (AFXQ bytes, status, d [total,32] -
+    None with keep_d=False, which needs a seed: unblind_issuances_wire_rng derives d again from it)."""
+    import ctypes as C
+    from . import check, lib
+    fn = lib().afx_group_blind_request_wire_rng if hasattr(ctx, "member") else lib().afx_blind_request_wire_rng
+    arr, keep = _blind_request_groups(groups, False)
+    rng = _device_rng(seed, stream)
+    out_len, cnt = C.c_size_t(0), C.c_size_t(0)
+    check(fn(ctx.h, arr, len(groups), C.byref(rng), None, None, 0, C.byref(out_len), None, 0, C.byref(cnt)))
+    out = np.zeros(max(1, out_len.value), np.uint8)
+    status = np.full(max(1, cnt.value), 255, np.uint8)
+    d = np.zeros((max(1, cnt.value), 32), np.uint8) if keep_d else None
+    check(fn(ctx.h, arr, len(groups), C.byref(rng), d.ctypes.data if keep_d else None, out.ctypes.data, out.size, C.byref(out_len), status.ctypes.data, status.size,
+             C.byref(cnt)))
+    return out[:out_len.value].tobytes(), status[:cnt.value], (d[:cnt.value] if keep_d else None)
+
+
+def _credential_out(total):
+    from . import CredentialOut
+    o = {k: np.zeros((max(1, total), 32), np.uint8) for k in ("t", "U", "V")}
+    return o, CredentialOut(*(o[k].ctypes.data for k in ("t", "U", "V")))
+
+
+def unblind_issuances_wire(ctx, issuances, requests, d):
+    """afx_unblind_issuances_wire (its group form for a Group): a stream of AFXJ sections, the AFXQ stream they answer and d [total,32]
+    in stream order -> (dict(t, U, V) [total,32] each: the credentials' t, U, V; status per item)"""
+    import ctypes as C
+    from . import check, lib
+    fn = lib().afx_group_unblind_issuances_wire if hasattr(ctx, "member") else lib().afx_unblind_issuances_wire
+    d = np.ascontiguousarray(d, dtype=np.uint8)
+    total = max(d.size // 32, len(issuances) // 160)   # (an AFXJ record is at least five cells)
+    o, co = _credential_out(total)
+    status = np.full(max(1, total), 255, np.uint8)
+    cnt = C.c_size_t(0)
+    check(fn(ctx.h, issuances, len(issuances), requests, len(requests), d.ctypes.data if d.size else None, C.byref(co), status.ctypes.data, min(total, d.size // 32),
+             C.byref(cnt)))
+    return {k: v[:cnt.value] for k, v in o.items()}, status[:cnt.value]
+
+
+def unblind_issuances_wire_rng(ctx, issuances, requests, seed, stream=0):
+    """afx_unblind_issuances_wire_rng (its group form for a Group): unblind_issuances_wire with d derived again on the device from the
+    (seed, stream) blind_request_wire_rng drew it from"""
+    import ctypes as C
+    from . import check, lib
+    fn = lib().afx_group_unblind_issuances_wire_rng if hasattr(ctx, "member") else lib().afx_unblind_issuances_wire_rng
+    rng = _device_rng(seed, stream)
+    total = len(issuances) // 160
+    o, co = _credential_out(total)
+    status = np.full(max(1, total), 255, np.uint8)
+    cnt = C.c_size_t(0)
+    check(fn(ctx.h, issuances, len(issuances), requests, len(requests), C.byref(rng), C.byref(co), status.ctypes.data, total, C.byref(cnt)))
+    return {k: v[:cnt.value] for k, v in o.items()}, status[:cnt.value]

@@ -702,8 +702,13 @@ int afx_group_show_wire(afx_group* group, afx_show_group* groups, size_t n_group
 #define AFX_DRAW_BLIND_U_WIDE 66u        /* 64 bytes */
 #define AFX_DRAW_BLIND_RPRIME_WIDE 67u   /* 64 bytes */
 #define AFX_DRAW_BLIND_ISSUE_SEED 68u    /* 32 bytes */
+/* the blind user's draws (afx_blind_request_wire_rng, afx_unblind_issuances_wire_rng: "Blind issuance on bytes: the user's doors" below) */
+#define AFX_DRAW_BLINDREQ_D_WIDE 69u     /* 64 bytes: d = from_bytes_mod_order_wide of them */
+#define AFX_DRAW_BLINDREQ_SEED 70u       /* 32 bytes */
+#define AFX_DRAW_BLINDREQ_R_WIDE(j) (71u + (uint32_t)(j))   /* 64 bytes; j < AFX_MAX_ATTRIBUTES: the j-th hidden position */
 #define AFX_DRAW_BYTES(label) (((label) == AFX_DRAW_T_WIDE || (label) == AFX_DRAW_U_WIDE || (label) == AFX_DRAW_Z_WIDE || \
-                                ((label) >= AFX_DRAW_BLIND_T_WIDE && (label) <= AFX_DRAW_BLIND_RPRIME_WIDE)) ? 64u : 32u)
+                                ((label) >= AFX_DRAW_BLIND_T_WIDE && (label) <= AFX_DRAW_BLIND_RPRIME_WIDE) || (label) == AFX_DRAW_BLINDREQ_D_WIDE || \
+                                ((label) >= AFX_DRAW_BLINDREQ_R_WIDE(0) && (label) <= AFX_DRAW_BLINDREQ_R_WIDE(31))) ? 64u : 32u)
 /* (declared apart from its typedef: unlike the batch structs above, the Rust shim does not bind it - it keeps the crate's explicit draws,
  * INTEGRATION.md - and tests/test_integration_layouts.py checks the typedef'd structs against the shim's) */
 struct afx_device_rng {
@@ -875,9 +880,9 @@ int afx_show_batchable_wire(afx_ctx* ctx, afx_show_group* groups, size_t n_group
  * which holds no secret, runs the fast ones.  Rows that hold r', x0 + x1*t, y_i*m_i or d*S1 are zeroed on the device, in stream
  * order, before the call completes.
  *
- * Out of scope: the user's doors (afx_blind_request and afx_unblind_issuances on bytes, and their draws), mixed small layouts in one
- * set of launches, coalescing, the batchable encoding of the two proofs, the Rust shim, bench.py.  The issuer's side on bytes, over
- * one context or a group and with its randomness drawn on the device, is "Blind issuance on bytes" below.  The host-pointer forms
+ * Out of scope: mixed small layouts in one set of launches, coalescing, the batchable encoding of the two proofs, the Rust shim,
+ * bench.py.  The issuer's side on bytes, over one context or a group and with its randomness drawn on the device, is "Blind issuance
+ * on bytes" below, the user's side "Blind issuance on bytes: the user's doors" behind it.  The host-pointer forms
  * take the context in turn and stage a call in one piece; counts beyond afx_ctx_set_chunk_items run as several passes.  `_dev`:
  * every pointer a device pointer, rows 16-byte aligned, the call asynchronous on afx_ctx_stream. */
 /* (declared apart from their typedefs, like afx_device_rng: the Rust shim does not bind them) */
@@ -1009,6 +1014,98 @@ int afx_issue_blind_wire_rng(afx_ctx* ctx, const uint8_t* blob, size_t len, cons
                              size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out);
 int afx_group_issue_blind_wire_rng(afx_group* group, const uint8_t* blob, size_t len, const afx_device_rng* rng, uint8_t* out,
                                    size_t out_cap, size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out);
+
+/* ---- Blind issuance on bytes: the user's doors -------------------------------------------------
+ * The user's side of the two sections above on bytes (normative): attribute columns in, AFXQ request sections out, and AFXJ issuance
+ * sections in, the credential's t, U, V out - with d, r_wide and rng_seed drawn on the device in the _rng forms, and over a group's
+ * devices.  With them the blind protocol runs on bytes end to end: attributes -> AFXQ -> afx_issue_blind_wire -> AFXJ -> t, U, V ->
+ * afx_show_wire -> AFXP -> verification.  Off unless called: nothing above changes.  Like the issuer's doors these calls take the
+ * context in turn, stage slice after slice on the context's two lanes and are never collected with other threads' calls.  The Rust
+ * shim and bench.py stay out of scope.
+ *
+ * afx_blind_request_wire: afx_blind_request over several groups of columns, one AFXQ v1 section per group out, in group order.
+ *  - status[i] answers item i of the stream, counting the earlier groups' items (there is no positions array); *count_out = their
+ *    number.  An item with status AFX_ST_OK gets a record that equals, byte for byte, what afx_blind_request followed by
+ *    afx_blind_request_wire_pack makes of the same inputs.  Every other item gets a record of zeros, written on the device, and the
+ *    column call's status (AFX_ST_MAC_CREATION).
+ *  - A group whose n_attributes is not the context's, or is 0, gets a section of zero records, all AFX_ST_MAC_CREATION (as the issuer's
+ *    door answers such a section).  Where n_attributes is 0 or above AFX_MAX_ATTRIBUTES the section has zero kinds: a header of
+ *    afx_blind_request_wire_header_bytes(0) bytes with n_attributes 0, cells_per_record 3 and n_responses 1 - no array has a length
+ *    beyond AFX_MAX_ATTRIBUTES.
+ *  - AFX_E_BAD_ARGS, with out and status untouched: a kind above AFX_ATTR_SECRET_POINT among the first min(n_attributes,
+ *    AFX_MAX_ATTRIBUTES) kinds of a group (no AFXQ header can carry it); a missing array (attrs.values, d, rnd.rng_seed, rnd.r_wide
+ *    where a position is hidden) in a group with count > 0; out_cap or status_cap too small.  The layout is checked for groups of count
+ *    0 too: their section still has a header.
+ *  - out == NULL: only *out_len and *count_out, from the kinds and the counts; no device work, the arrays may be NULL.
+ *  - Per slice afx_blind_request_dev writes D, A, B, the challenge and the responses into rows that lie behind the staged value rows,
+ *    k_soa_to_aos makes the records of those rows and the value rows of the revealed positions (failed items zeroed), and the records
+ *    come back in one fetch.  Groups run one after another; groups of one layout are not merged.
+ *
+ * afx_unblind_issuances_wire: afx_unblind_issuances over a stream of AFXJ sections and the AFXQ stream they answer.
+ *  - requests: the AFXQ stream the user sent (the user's own D, A, B and the revealed values are read; hidden values are not needed).
+ *    d: [total] Sc in stream order.  out: t, U, V, [total] each in stream order, ready to be afx_credentials_soa's t, U, V.
+ *  - Both streams are parsed in full before anything runs.  The k-th AFXJ section pairs with the k-th AFXQ section: the section counts
+ *    must match and each pair must agree on count, n_attributes and kinds.  Anything else, or a malformed section anywhere, is
+ *    AFX_E_BAD_ARGS with nothing written; so are status_cap below the item count and a missing array.
+ *  - A pair whose n_attributes is not the context's (or is 0), or whose AFXJ n_responses is not the context's n + 6, fails every item
+ *    with AFX_ST_VERIFICATION_FAILURE, answered on the host as the column call answers it.
+ *  - t and U are the record's, V = S2 - d*S1; the statuses and V equal afx_unblind_issuances' on the unpacked columns.  A failed item
+ *    gets zeros in all three, written on the device before the call completes.  The zero records the issuer's door writes for the
+ *    requests it refused fail here like any other issuance that does not verify.
+ *  - Pairs of one layout are merged into one batch wherever they stand; a batch larger than afx_ctx_set_chunk_items runs as slices.  Per
+ *    slice two k_aos_to_soa launches (the AFXJ cells, then the AFXQ cells) fill one row region, afx_unblind_issuances_dev runs on
+ *    it, and k_soa_to_aos copies t, U and V out, a row each.
+ *
+ * The _rng forms ("Randomness drawn on the device" above), specified as equivalences:
+ *  - afx_blind_request_wire_rng does not read the groups' d and rnd.  Item i of the stream uses d = from_bytes_mod_order_wide(draw(seed,
+ *    stream, i, AFX_DRAW_BLINDREQ_D_WIDE)), reduced on the device (k_reduce_wide), r_wide[j] = draw(seed, stream, i,
+ *    AFX_DRAW_BLINDREQ_R_WIDE(j)) for the j-th hidden position and rng_seed = draw(seed, stream, i, AFX_DRAW_BLINDREQ_SEED); it returns
+ *    the bytes, statuses, lengths and error codes afx_blind_request_wire returns on those draws.  d_out, [total] Sc, receives d, zeros
+ *    for a failed item; it may be NULL only when rng->seed is given - with a seed from getrandom(2) and no d_out the user could
+ *    never unblind: AFX_E_BAD_ARGS.  The staged seed, the d_wide rows and the d rows are zeroed on the device before the call completes,
+ *    failures included.  d is copied out of its scratch row - into a staged output row, itself zeroed on the device behind the copy
+ *    that fetches it - only when d_out is given: with d_out == NULL no d leaves the device or outlives the call there.  What a caller
+ *    asked for in d_out is an output like any other on the host (it passes the library's pinned result buffer on its way).
+ *  - afx_unblind_issuances_wire_rng needs rng->seed (NULL: AFX_E_BAD_ARGS) and derives d again on the device from the same (seed,
+ *    stream, index): a user who keeps the 32-byte seed and the AFXQ bytes holds no per-item secret, and d never crosses the bus.  It
+ *    returns what afx_unblind_issuances_wire returns on the re-derived d.
+ * The group forms split every group (the request door) or merged batch (the unblinding door) over the members (afx_shard_bounds), one
+ * host thread per member; a stream of at most afx_ctx_set_small_batch_items items (member 0's) goes whole to one member, in turn.
+ * The bytes equal the one-context call's: a draw depends on the item's index in the stream only. */
+/* (declared apart from their typedefs, like the other blind structs: the Rust shim does not bind them) */
+struct afx_blind_request_group {
+  afx_attributes_soa attrs;            /* values [n][count], all positions            */
+  const uint8_t* d;                    /* [count] Sc                                  */
+  afx_blind_request_randomness rnd;    /* r_wide [h][count][64], rng_seed [count][32] */
+  size_t count;
+};
+typedef struct afx_blind_request_group afx_blind_request_group;
+struct afx_credential_out {
+  uint8_t* t;                          /* [total] Sc, stream order */
+  uint8_t* U;                          /* [total] Pt               */
+  uint8_t* V;                          /* [total] Pt               */
+};
+typedef struct afx_credential_out afx_credential_out;
+int afx_blind_request_wire(afx_ctx* ctx, const afx_blind_request_group* groups, size_t n_groups, uint8_t* out, size_t out_cap, size_t* out_len,
+                           uint8_t* status, size_t status_cap, size_t* count_out);
+int afx_group_blind_request_wire(afx_group* group, const afx_blind_request_group* groups, size_t n_groups, uint8_t* out, size_t out_cap,
+                                 size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out);
+int afx_blind_request_wire_rng(afx_ctx* ctx, const afx_blind_request_group* groups, size_t n_groups, const afx_device_rng* rng, uint8_t* d_out,
+                               uint8_t* out, size_t out_cap, size_t* out_len, uint8_t* status, size_t status_cap, size_t* count_out);
+int afx_group_blind_request_wire_rng(afx_group* group, const afx_blind_request_group* groups, size_t n_groups, const afx_device_rng* rng,
+                                     uint8_t* d_out, uint8_t* out, size_t out_cap, size_t* out_len, uint8_t* status, size_t status_cap,
+                                     size_t* count_out);
+int afx_unblind_issuances_wire(afx_ctx* ctx, const uint8_t* issuances, size_t issuances_len, const uint8_t* requests, size_t requests_len,
+                               const uint8_t* d, const afx_credential_out* out, uint8_t* status, size_t status_cap, size_t* count_out);
+int afx_group_unblind_issuances_wire(afx_group* group, const uint8_t* issuances, size_t issuances_len, const uint8_t* requests,
+                                     size_t requests_len, const uint8_t* d, const afx_credential_out* out, uint8_t* status, size_t status_cap,
+                                     size_t* count_out);
+int afx_unblind_issuances_wire_rng(afx_ctx* ctx, const uint8_t* issuances, size_t issuances_len, const uint8_t* requests, size_t requests_len,
+                                   const afx_device_rng* rng, const afx_credential_out* out, uint8_t* status, size_t status_cap,
+                                   size_t* count_out);
+int afx_group_unblind_issuances_wire_rng(afx_group* group, const uint8_t* issuances, size_t issuances_len, const uint8_t* requests,
+                                         size_t requests_len, const afx_device_rng* rng, const afx_credential_out* out, uint8_t* status,
+                                         size_t status_cap, size_t* count_out);
 
 /* ---- setup helpers (cold path; still GPU arithmetic) ---------------------------------------- */
 
