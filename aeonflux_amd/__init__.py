@@ -494,9 +494,10 @@ class Context:
         """concurrent small host-pointer calls share launch sets (on by default); max_items=0 switches it off (afx_ctx_set_coalescing)"""
         check(lib().afx_ctx_set_coalescing(self.h, max_wait_us, max_items))
 
-    def merlin_challenges(self, label, ops, fields, count):
+    def merlin_challenges(self, label, ops, fields, count, out=None):
         """a merlin transcript over a batch (afx_merlin_challenges).  ops: ("append", label, bytes) | ("append_field", label, index) |
-        ("challenge", label, n) last; fields: list of uint8 arrays [count][32].  Returns [count][64] (the first n bytes: the challenge)"""
+        ("challenge", label, n) last; fields: list of uint8 arrays [count][32].  Returns [count][64] (the first n bytes: the challenge);
+        out: the caller's own C-contiguous uint8 array of at least count rows of 64 bytes to write them to (and return) instead"""
         import numpy as np
         u32 = lambda v: int(v).to_bytes(4, "little")
         bs = lambda b: u32(len(b)) + bytes(b)
@@ -512,7 +513,10 @@ class Context:
                 raise ValueError(op[0])
         keep = [np.ascontiguousarray(f, dtype=np.uint8) for f in fields]
         ptrs = (C.c_void_p * max(1, len(keep)))(*[f.ctypes.data for f in keep])
-        out = np.zeros((count, 64), np.uint8)
+        if out is None:
+            out = np.zeros((count, 64), np.uint8)
+        elif out.dtype != np.uint8 or not out.flags.c_contiguous or out.ndim != 2 or out.shape[1] != 64 or out.shape[0] < count:
+            raise ValueError("out: a C-contiguous uint8 array [>= count][64]")
         check(lib().afx_merlin_challenges(self.h, script, len(script), ptrs, len(keep), count, out.ctypes.data))
         return out
 

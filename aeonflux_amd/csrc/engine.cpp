@@ -1393,6 +1393,7 @@ int run_plans(afx_ctx* ctx, int lane, Plan* const* plans, size_t n) {
       }
       case L_HASH:
         // small passes: the permutation spread over 32 lanes per item (kernels.hip k_hash_coop), while the device has lanes to spare
+        if (coop) tl.kind = AFX_HASH_COOP_ON_WAVE(max_count, nrows, ctx->variants) ? (int)T_HASH_COOP64 : (int)T_HASH_COOP;   // (the launcher's own rule: plan.h)
         if (coop) AFX_HIP(afxk_hash_coop(s, (const afx_hash_program*)jobs, nrows, rw, passes, max_count, ctx->variants));
         else AFX_HIP(afxk_hash(s, (const afx_hash_program*)jobs, nrows, rw, passes, max_count));
         break;
@@ -1446,8 +1447,23 @@ int run_plans(afx_ctx* ctx, int lane, Plan* const* plans, size_t n) {
 // ------------------------------------------------------------------------------------------------
 // SchnorrBuilder
 // ------------------------------------------------------------------------------------------------
+// The framing log (tests/hostsim/framing_log.cpp, built with -DAFX_FRAMING_LOG; the shipped library is built without): every
+// builder's labels, allocations and constraints as text lines -
+//   new <transcript label> <proof label> | scalar <label> | point <label> | constrain <lhs point> <scalar>:<point>,...
+// tab-separated, variables by their allocation index: the form oracle/zkp.c logs, compared with the reference's source text by
+// tests/test_framing.py.
+#ifdef AFX_FRAMING_LOG
+static std::string g_framing_log;   // (the test program is single-threaded)
+extern "C" const char* afx_framing_log_text(void) { return g_framing_log.c_str(); }
+extern "C" void afx_framing_log_clear(void) { g_framing_log.clear(); }
+#define AFX_FRAMING(text) (g_framing_log += (text))
+#else
+#define AFX_FRAMING(text) ((void)0)
+#endif
+
 SchnorrBuilder::SchnorrBuilder(Assembler& as, const char* transcript_label, const char* proof_label)
     : as_(as), sim_(transcript_label) {
+  AFX_FRAMING(std::string("new\t") + transcript_label + "\t" + proof_label + "\n");
   // TranscriptProtocol::domain_sep (zkp toolbox)
   sim_.append_message_const("dom-sep", (const uint8_t*)"schnorrzkp/1.0/ristretto255", 27);
   sim_.append_message_const("dom-sep", (const uint8_t*)proof_label, strlen(proof_label));
@@ -1459,11 +1475,13 @@ int SchnorrBuilder::field_of(const uint8_t* dev) {
   return (int)fields_.size() - 1;
 }
 int SchnorrBuilder::allocate_scalar(const char* label, const ScalarVar& v) {
+  AFX_FRAMING(std::string("scalar\t") + label + "\n");
   sim_.append_message_const("scvar", (const uint8_t*)label, strlen(label));
   scalars_.push_back(v);
   return (int)scalars_.size() - 1;
 }
 int SchnorrBuilder::allocate_point(const char* label, const PointVar& p) {
+  AFX_FRAMING(std::string("point\t") + label + "\n");
   sim_.append_message_const("ptvar", (const uint8_t*)label, strlen(label));
   if (p.is_const) {
     const Enc& e = p.neg ? as_.ctx->gen_neg_enc[p.gen] : as_.ctx->gen_enc[p.gen];
@@ -1479,7 +1497,14 @@ int SchnorrBuilder::allocate_point(const char* label, const PointVar& p) {
   point_labels_.push_back(label);
   return (int)points_.size() - 1;
 }
-void SchnorrBuilder::constrain(int lhs, const std::vector<std::pair<int, int>>& terms) { constraints_.push_back({ lhs, terms }); }
+void SchnorrBuilder::constrain(int lhs, const std::vector<std::pair<int, int>>& terms) {
+#ifdef AFX_FRAMING_LOG
+  std::string line = "constrain\t" + std::to_string(lhs) + "\t";
+  for (size_t k = 0; k < terms.size(); k++) line += (k ? "," : "") + std::to_string(terms[k].first) + ":" + std::to_string(terms[k].second);
+  AFX_FRAMING(line + "\n");
+#endif
+  constraints_.push_back({ lhs, terms });
+}
 
 afx_msm_term SchnorrBuilder::term_for(const uint8_t* scalar, uint32_t stride, const PointVar& p, bool negate, std::vector<afx_scalarop_job>* pre_ops) {
   afx_msm_term t;

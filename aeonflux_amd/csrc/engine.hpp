@@ -259,8 +259,8 @@ struct afx_ctx {
   struct TimedLaunch { int kind; hipEvent_t start, stop; };
   std::vector<TimedLaunch> timed;          // recorded, not yet read back
   std::vector<hipEvent_t> event_pool;      // recycled events
-  double kind_ms[24] = { 0 };
-  uint64_t kind_launches[24] = { 0 };
+  double kind_ms[32] = { 0 };               // indexed by afx::LaunchKind and, past L_KINDS, afx::TimingSlot
+  uint64_t kind_launches[32] = { 0 };
 };
 
 namespace afx {
@@ -268,6 +268,10 @@ namespace afx {
 // L_MSM_WINDOW keeps the slot the single k_msm kernel had (timing names: statements.cpp KIND_NAMES)
 enum LaunchKind { L_FILL_BAD, L_DECODE, L_SCCHECK, L_POINTOP, L_SCALAROP, L_MSM_WINDOW, L_HASH, L_FROM_UNIFORM, L_REDUCE_WIDE, L_COPY, L_FINISH,
                   L_MSM_FIXED, L_MSM_NAF, L_MSM_TABLES, L_COMPRESS, L_POINTSUM, L_NEGENC, L_TABLE_AFFINE, L_POWERS, L_COEF, L_SHA512, L_ENCODE, L_MASK, L_KINDS };
+// Timing slots past the launch kinds: the two cooperative kernels an L_HASH launch may take instead of k_hash (kernels.hip
+// afxk_hash_coop), counted apart so that a test can say which kernel it ran.  "k_hash" (afx_ctx_get_timing) stays the three together.
+enum TimingSlot { T_HASH_COOP = L_KINDS, T_HASH_COOP64, T_SLOTS };
+static_assert(T_SLOTS <= sizeof(afx_ctx::kind_ms) / sizeof(double), "a timing slot per launch kind and cooperative hash kernel");
 // the kernels whose grid rows WALK a range of the launch's jobs (afx_walk_row) instead of taking one job each (afx_row)
 inline bool walks(LaunchKind k) { return k == L_COMPRESS || k == L_NEGENC || k == L_TABLE_AFFINE; }
 

@@ -2078,8 +2078,7 @@ hipError_t afxk_powers(hipStream_t s, const afx_powers_job* jobs, uint32_t njobs
 }
 hipError_t afxk_hash_coop(hipStream_t s, const afx_hash_program* progs, uint32_t nprogs, const afx_row* rows, const afx_pass* passes, uint32_t max_count, uint32_t variants) {
   // a wave per (item, program) while that leaves the device mostly idle (AFX_KV_HASH_HALF_WAVE: tests, the 32-lane groups always)
-  const bool wave_on = !(variants & AFX_KV_HASH_HALF_WAVE);
-  if (wave_on && (uint64_t)max_count * nprogs <= 2048) {
+  if (AFX_HASH_COOP_ON_WAVE(max_count, nprogs, variants)) {
     const uint32_t b64 = max_count <= 1 ? 64u : max_count <= 2 ? 128u : (uint32_t)AFX_BLOCK, per64 = b64 / 64;
     hipLaunchKernelGGL(k_hash_coop64, dim3((max_count + per64 - 1) / per64, nprogs), dim3(b64), 0, s, progs, rows, passes);
     return hipGetLastError();

@@ -59,6 +59,11 @@
                                           the launch stay within this: beyond it the lane groups queue up and one lane per item is as
                                           fast (measured: issue, 1-2 programs per launch, gains up to 4096 items; show and verify,
                                           5 programs, up to ~800: tools/small_call_latency.py) */
+#define AFX_HASH_WAVE_GROUPS 2048       /* of those, a launch this small takes a wave per (item, program) - k_hash_coop64 - unless
+                                          AFX_KV_HASH_HALF_WAVE is set.  One rule for the launcher (kernels.hip afxk_hash_coop) and
+                                          for the engine's per-kernel launch accounting (engine.cpp) */
+#define AFX_HASH_COOP_ON_WAVE(max_count, nprogs, variants) \
+  (!((variants) & AFX_KV_HASH_HALF_WAVE) && (uint64_t)(max_count) * (nprogs) <= AFX_HASH_WAVE_GROUPS)
 /* field multiplications / squarings of one ristretto255 decoding / encoding as ge.cuh implements them
  * (measured on the host build of that header: tests/test_device_arith_on_host.py) */
 #define AFX_DECODE_MUL 27

@@ -36,10 +36,12 @@ extern "C" const char* afx_last_error(void) { return afx::last_error(); }
 extern "C" uint32_t afx_ctx_n_attributes(const afx_ctx* ctx) { return ctx ? ctx->n : 0; }
 extern "C" void* afx_ctx_stream(const afx_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
-// indexed by afx::LaunchKind.  "k_msm" (afx_ctx_get_timing) = the three chain kernels + the table kernel together
+// indexed by afx::LaunchKind, then afx::TimingSlot.  "k_msm" (afx_ctx_get_timing) = the three chain kernels + the table kernel together;
+// "k_hash" = the one-lane kernel + the two cooperative ones together (the slot L_HASH itself holds the one-lane kernel alone)
 static const char* const KIND_NAMES[] = { "k_fill_u32", "k_decode", "k_sccheck", "k_pointop", "k_scalarop", "k_msm_window", "k_hash",
-                                          "k_from_uniform", "k_reduce_wide", "copy", "k_finish", "k_msm_fixed", "k_msm_naf", "k_msm_tables", "k_compress2x", "k_pointsum", "k_negenc", "k_table_affine", "k_powers", "k_coef", "k_sha512", "k_encode_to_group", "k_mask_rows" };
-static_assert(sizeof KIND_NAMES / sizeof KIND_NAMES[0] == afx::L_KINDS, "one name per launch kind");
+                                          "k_from_uniform", "k_reduce_wide", "copy", "k_finish", "k_msm_fixed", "k_msm_naf", "k_msm_tables", "k_compress2x", "k_pointsum", "k_negenc", "k_table_affine", "k_powers", "k_coef", "k_sha512", "k_encode_to_group", "k_mask_rows",
+                                          "k_hash_coop", "k_hash_coop64" };
+static_assert(sizeof KIND_NAMES / sizeof KIND_NAMES[0] == afx::T_SLOTS, "one name per launch kind and timing slot");
 static int drain_timing(afx_ctx* c) {
   for (auto& L : c->lane)
     if (L.stream) AFX_HIP(hipStreamSynchronize(L.stream));
@@ -196,7 +198,7 @@ extern "C" int afx_ctx_set_timing(afx_ctx* c, int enable) try {
   AFX_HIP(hipSetDevice(c->device));
   int rc = drain_timing(c);
   if (rc) return rc;
-  for (int k = 0; k < (int)afx::L_KINDS; k++) { c->kind_ms[k] = 0; c->kind_launches[k] = 0; }
+  for (int k = 0; k < (int)afx::T_SLOTS; k++) { c->kind_ms[k] = 0; c->kind_launches[k] = 0; }
   if (c->d_consts.p) AFX_HIP(hipMemsetAsync(c->clock_probe(), 0, 16 * AFX_CLOCK_SLOTS, c->stream));
   { std::lock_guard<std::mutex> sg(c->settings_mu); c->timing = enable != 0; }
   return AFX_OK;
@@ -242,6 +244,11 @@ extern "C" int afx_ctx_get_timing(afx_ctx* c, const char* kernel, double* total_
   if (strcmp(kernel, "k_msm") == 0) {
     *total_ms = 0; *launches = 0;
     for (int k : { (int)L_MSM_WINDOW, (int)L_MSM_FIXED, (int)L_MSM_NAF, (int)L_MSM_TABLES }) { *total_ms += c->kind_ms[k]; *launches += c->kind_launches[k]; }
+    return AFX_OK;
+  }
+  if (strcmp(kernel, "k_hash") == 0) {
+    *total_ms = 0; *launches = 0;
+    for (int k : { (int)L_HASH, (int)T_HASH_COOP, (int)T_HASH_COOP64 }) { *total_ms += c->kind_ms[k]; *launches += c->kind_launches[k]; }
     return AFX_OK;
   }
   for (size_t k = 0; k < sizeof KIND_NAMES / sizeof KIND_NAMES[0]; k++)

@@ -304,8 +304,9 @@ int afx_ctx_get_plan_cache_stats(afx_ctx* ctx, afx_plan_cache_stats* out);
  * set_timing(ctx, 1) resets the counters and starts recording every launch; get_timing synchronises the
  * stream and returns the summed duration and launch count of one kernel: "k_msm_window", "k_msm_naf", "k_msm_fixed"
  * (the three multiscalar kernels: per-item windows, uniform width-5 NAF terms, fixed bases only), "k_msm_tables", or
- * "k_msm" for those four together; "k_hash", "k_decode", "k_pointop", "k_scalarop", "k_sccheck", "k_finish",
- * "k_from_uniform", "k_reduce_wide", "k_fill_u32". */
+ * "k_msm" for those four together; "k_hash" (every transcript launch, whichever kernel it took), of which "k_hash_coop" and
+ * "k_hash_coop64" are the launches of the two cooperative kernels (32 lanes / a wave per item; the rest took one lane per item);
+ * "k_decode", "k_pointop", "k_scalarop", "k_sccheck", "k_finish", "k_from_uniform", "k_reduce_wide", "k_fill_u32". */
 int afx_ctx_set_timing(afx_ctx* ctx, int enable);
 int afx_ctx_get_timing(afx_ctx* ctx, const char* kernel, double* total_ms, uint64_t* launches);
 /* The core clock the k_msm_window launches recorded since set_timing(ctx, 1) actually ran at, in MHz (0 if none ran): one lane of

@@ -321,6 +321,40 @@ def debug_last():
     return [commits.raw[32 * i:32 * i + 32] for i in range(n.value)], ch.raw
 
 
+def framing_log(on=True):
+    """switch this thread's framing log on (cleared) or off: zkp.c records every statement's labels, allocations and constraints"""
+    lib().afxo_framing_log(1 if on else 0)
+
+
+def framing_log_read():
+    """the statements logged since framing_log(True), one dict each: transcript, proof, allocs [[kind, label]], constraints
+    [[lhs point, [[scalar, point], ...]]] with variables as allocation indices (scalars and points count apart)"""
+    o = _buf(1 << 16)
+    lib().afxo_framing_log_read.restype = C.c_long
+    n = lib().afxo_framing_log_read(o, len(o))
+    if n < 0:
+        raise ValueError("the framing log overflowed")
+    return parse_framing_log(o.raw[:n].decode())
+
+
+def parse_framing_log(text):
+    """the line format shared by the oracle's log and the engine's (tests/hostsim/framing_log.cpp)"""
+    out = []
+    for line in text.split("\n"):
+        if not line:
+            continue
+        f = line.split("\t")
+        if f[0] == "new":
+            out.append(dict(transcript=f[1], proof=f[2], allocs=[], constraints=[]))
+        elif f[0] in ("scalar", "point"):
+            out[-1]["allocs"].append([f[0], f[1]])
+        elif f[0] == "constrain":
+            out[-1]["constraints"].append([int(f[1]), [[int(x) for x in t.split(":")] for t in f[2].split(",") if t]])
+        else:
+            raise ValueError("framing log: " + line)
+    return out
+
+
 # ---- batch forms over numpy struct-of-arrays (tests/test_gpu_full_size.py) ----
 
 def host_threads():

@@ -95,6 +95,10 @@ void afxo_merlin_simple(const uint8_t* label, size_t llen, const uint8_t* l1, si
 long afxo_merlin_script(const uint8_t* script, size_t len, const uint8_t* fields, uint32_t n_fields, uint8_t* out, size_t cap);
 void afxo_debug_last(uint8_t* commits, int* ncommit, uint8_t challenge[32]);
 void afxo_debug_reset(void);
+/* the framing log of this thread's statements (zkp.c): on != 0 clears it and switches it on, 0 switches it off; read returns the
+ * length of the text copied to `out`, or -1 if it overflowed or does not fit */
+void afxo_framing_log(int on);
+long afxo_framing_log_read(char* out, size_t cap);
 /* opt-in strict mode (not the reference's behaviour; see oracle/aeonflux.c) */
 void afxo_ctx_set_strict(afxo_ctx* c, int strict);   /* ncommit = 0 until the next prove/verify reaches its commitments */
 #endif

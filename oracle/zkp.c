@@ -11,6 +11,41 @@ __thread int zkp_debug_ncommit;
 __thread uint8_t zkp_debug_commit[ZKP_MAX_CONSTRAINTS][32];
 __thread uint8_t zkp_debug_challenge[32];
 
+/* The framing log (tests/test_framing.py): while it is on, every zkp_init / allocation / constraint of this thread adds a line -
+ *   new <transcript label> <proof label> | scalar <label> | point <label> | constrain <lhs point> <scalar>:<point>,...
+ * tab-separated, variables by their allocation index - so that what a statement feeds the transcript, and in which order, can be
+ * compared with the reference's source text.  Off (the default) it costs one branch on a thread-local flag per call. */
+#define ZKP_LOG_CAP (1 << 16)
+static __thread int zkp_log_on;
+static __thread size_t zkp_log_len;
+static __thread char zkp_log[ZKP_LOG_CAP];
+static void log_text(const char* s) {
+  size_t n = strlen(s);
+  if (zkp_log_len + n >= ZKP_LOG_CAP) { zkp_log_on = -1; return; }   /* overflow: reported by afxo_framing_log_read */
+  memcpy(zkp_log + zkp_log_len, s, n);
+  zkp_log_len += n;
+}
+static void log_int(int v) {
+  char b[16];
+  int n = 0;
+  if (v < 0) { log_text("-"); v = -v; }
+  do { b[n++] = (char)('0' + v % 10); v /= 10; } while (v);
+  char r[17];
+  for (int i = 0; i < n; i++) r[i] = b[n - 1 - i];
+  r[n] = 0;
+  log_text(r);
+}
+void afxo_framing_log(int on) {
+  zkp_log_on = on ? 1 : 0;
+  zkp_log_len = 0;
+}
+/* copies the log (no terminator) and returns its length; -1: it overflowed or `cap` is too small */
+long afxo_framing_log_read(char* out, size_t cap) {
+  if (zkp_log_on < 0 || zkp_log_len > cap) return -1;
+  memcpy(out, zkp_log, zkp_log_len);
+  return (long)zkp_log_len;
+}
+
 static void append(zkp_cs* z, const char* label, const uint8_t* msg, size_t mlen) {
   merlin_append_message(&z->t, (const uint8_t*)label, strlen(label), msg, mlen);
 }
@@ -18,6 +53,7 @@ static void append(zkp_cs* z, const char* label, const uint8_t* msg, size_t mlen
 void zkp_init(zkp_cs* z, int is_prover, const char* transcript_label, const char* proof_label) {
   afxo_init_constants();
   memset(z, 0, sizeof *z);
+  if (zkp_log_on > 0) { log_text("new\t"); log_text(transcript_label); log_text("\t"); log_text(proof_label); log_text("\n"); }
   z->is_prover = is_prover;
   merlin_new(&z->t, (const uint8_t*)transcript_label, strlen(transcript_label));
   /* TranscriptProtocol::domain_sep */
@@ -26,12 +62,14 @@ void zkp_init(zkp_cs* z, int is_prover, const char* transcript_label, const char
 }
 
 int zkp_alloc_scalar(zkp_cs* z, const char* label, const sc* value) {
+  if (zkp_log_on > 0) { log_text("scalar\t"); log_text(label); log_text("\n"); }
   append(z, "scvar", (const uint8_t*)label, strlen(label));
   if (value) z->scalars[z->n_scalars] = *value;
   return z->n_scalars++;
 }
 
 int zkp_alloc_point_prover(zkp_cs* z, const char* label, const ge* p) {
+  if (zkp_log_on > 0) { log_text("point\t"); log_text(label); log_text("\n"); }
   int i = z->n_points++;
   z->points[i] = *p;
   z->point_labels[i] = label;
@@ -42,6 +80,7 @@ int zkp_alloc_point_prover(zkp_cs* z, const char* label, const ge* p) {
 }
 
 int zkp_alloc_point_verifier(zkp_cs* z, const char* label, const uint8_t enc[32]) {
+  if (zkp_log_on > 0) { log_text("point\t"); log_text(label); log_text("\n"); }
   int i = z->n_points++;
   z->point_labels[i] = label;
   memcpy(z->enc[i], enc, 32);
@@ -55,6 +94,11 @@ int zkp_alloc_point_verifier(zkp_cs* z, const char* label, const uint8_t enc[32]
 }
 
 void zkp_constrain(zkp_cs* z, int lhs, int n, const int* scs, const int* pts) {
+  if (zkp_log_on > 0) {
+    log_text("constrain\t"); log_int(lhs); log_text("\t");
+    for (int i = 0; i < n; i++) { if (i) log_text(","); log_int(scs[i]); log_text(":"); log_int(pts[i]); }
+    log_text("\n");
+  }
   zkp_constraint* c = &z->cs[z->n_constraints++];
   c->lhs = lhs;
   c->n = n;

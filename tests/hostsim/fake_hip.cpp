@@ -12,6 +12,7 @@
 #include <map>
 #include <mutex>
 #include "../../aeonflux_amd/csrc/kernels.h"
+#include "../../aeonflux_amd/csrc/strobe_sim.hpp"   // (keccak_f1600_host: the `hash` knob)
 
 // Knobs a test sets WHILE other threads are inside the library (environment variables cannot be changed then):
 //   sync_us    every hipStreamSynchronize sleeps this long - a launch set "computes" for a while, so that calls of other threads
@@ -19,11 +20,16 @@
 //   fail_next  the next `fail_next` finishing launches fail (a flush that fails with calls of several threads in it)
 //   echo       a pass's status bytes are the first byte of each item of the first scalar array the pass checks (the challenge
 //              row of a verification): a test sees that every caller gets the result of ITS OWN rows
-static std::atomic<int> g_sync_us{ 0 }, g_fail_next{ 0 }, g_echo{ 0 };
+//   hash       the one exception to "nothing computes": a hash launch runs its programs word by word as kernels.hip k_hash does and
+//              stores what a record squeezes as 64 raw bytes (AFX_SQ_WIDE_OUT; the reduced forms need scalar arithmetic and stay
+//              no-ops) - a scripted transcript (afx_merlin_challenges) then returns real challenges, so that the compiled byte
+//              schedule (strobe_sim.hpp StrobeSim::to_device) can be compared with the oracle without a GPU
+static std::atomic<int> g_sync_us{ 0 }, g_fail_next{ 0 }, g_echo{ 0 }, g_hash{ 0 };
 extern "C" void afx_fake_set(const char* what, int v) {
   if (!strcmp(what, "sync_us")) g_sync_us = v;
   else if (!strcmp(what, "fail_next")) g_fail_next = v;
   else if (!strcmp(what, "echo")) g_echo = v;
+  else if (!strcmp(what, "hash")) g_hash = v;
 }
 // the CPUs the thread that launched a device's latest finishing kernel was allowed on (bit k = CPU k, the first 64): a test reads
 // where a group's member threads ran (group.cpp PinScope)
@@ -248,6 +254,34 @@ hipError_t afxk_hash(hipStream_t, const afx_hash_program* p, uint32_t n, const a
         if (q.records[r].w[w].field >= 0) { if ((uint32_t)q.records[r].w[w].field >= q.n_fields) return hipErrorInvalidValue; CHECK_PTR(q.fields[q.records[r].w[w].field]); }
     for (uint32_t k = 0; k < q.n_outs; k++) CHECK_PTR(q.outs[k]);
     CHECK_PTR(q.challenge);
+    if (!g_hash.load() || (!q.init_state && !q.load_state)) continue;
+    const uint32_t count = pass_of(passes, rows, i).count;
+    for (uint32_t item = 0; item < count; item++) {   // kernels.hip k_hash, a lane's work
+      uint64_t st[25];
+      for (int w = 0; w < 25; w++) st[w] = q.load_state ? q.load_state[(size_t)w * count + item] : q.init_state[w];
+      for (uint32_t r = 0; r < q.n_records; r++) {
+        const afx_hash_record& rec = q.records[r];
+        for (int w = 0; w < 21; w++) {
+          const afx_hash_word& hw = rec.w[w];
+          uint64_t v = hw.c;
+          if (hw.field >= 0) {
+            const uint8_t* f = q.fields[hw.field] + 32ull * item;
+            uint64_t lo = 0, hi = 0;
+            if (hw.q >= 0) memcpy(&lo, f + 8 * hw.q, 8);
+            if (hw.q < 3) memcpy(&hi, f + 8 * (hw.q + 1), 8);
+            const uint32_t sh = 8u * hw.r;
+            v ^= (sh ? ((lo >> sh) | (hi << (64u - sh))) : lo) & hw.fmask;
+          }
+          st[w] = (st[w] & hw.keep) ^ v;
+        }
+        afx::keccak_f1600_host(st);
+        if (rec.squeeze == AFX_SQ_WIDE_OUT) {
+          if (rec.squeeze_out >= q.n_outs) return hipErrorInvalidValue;
+          memcpy(q.outs[rec.squeeze_out] + 64ull * item, st, 64);
+        }
+      }
+      if (q.save_state) for (int w = 0; w < 25; w++) q.save_state[(size_t)w * count + item] = st[w];
+    }
   }
   return hipSuccess;
 }

@@ -125,6 +125,7 @@ class Transcript:
             self.strobe = _strobe
             return
         self.strobe = Strobe128(b"Merlin v1.0")
+        self.label = label      # (kept for the framing log of tests/pyref/zkp.py)
         self.append_message(b"dom-sep", label)
 
     def append_message(self, label, message):

@@ -8,6 +8,19 @@ class ProofError(Exception):
     pass
 
 
+# The framing log (tests/test_framing.py): a list switches it on; every Prover / Verifier made while it is set appends a dict
+# - transcript (the merlin label, from the caller), proof, allocs [[kind, label]], constraints [[lhs point, [[scalar, point], ...]]],
+# variables as allocation indices (scalars and points count apart) - the form oracle.framing_log_read() returns.
+LOG = None
+
+
+def _log_new(transcript, proof_label):
+    if LOG is None:
+        return None
+    LOG.append(dict(transcript=getattr(transcript, "label", b"").decode(), proof=proof_label.decode(), allocs=[], constraints=[]))
+    return LOG[-1]
+
+
 def _domain_sep(t, label):
     t.append_message(b"dom-sep", b"schnorrzkp/1.0/ristretto255")
     t.append_message(b"dom-sep", label)
@@ -25,15 +38,20 @@ def _challenge(t):
 class Prover:
     def __init__(self, proof_label, transcript):
         self.t = transcript
+        self.log = _log_new(transcript, proof_label)
         _domain_sep(self.t, proof_label)
         self.scalars, self.points, self.labels, self.constraints = [], [], [], []
 
     def allocate_scalar(self, label, value):
+        if self.log is not None:
+            self.log["allocs"].append(["scalar", label.decode()])
         self.t.append_message(b"scvar", label)
         self.scalars.append(value % R.L)
         return len(self.scalars) - 1
 
     def allocate_point(self, label, point):
+        if self.log is not None:
+            self.log["allocs"].append(["point", label.decode()])
         enc = R.encode(point)
         _append_point(self.t, b"ptvar", label, enc)
         self.points.append(point)
@@ -41,6 +59,8 @@ class Prover:
         return len(self.points) - 1
 
     def constrain(self, lhs, terms):
+        if self.log is not None:
+            self.log["constraints"].append([lhs, [[sv, pv] for sv, pv in terms]])
         self.constraints.append((lhs, list(terms)))
 
     def prove_compact(self, external_random32):
@@ -65,16 +85,21 @@ class Prover:
 class Verifier:
     def __init__(self, proof_label, transcript):
         self.t = transcript
+        self.log = _log_new(transcript, proof_label)
         _domain_sep(self.t, proof_label)
         self.n_scalars = 0
         self.points, self.labels, self.constraints = [], [], []
 
     def allocate_scalar(self, label):
+        if self.log is not None:
+            self.log["allocs"].append(["scalar", label.decode()])
         self.t.append_message(b"scvar", label)
         self.n_scalars += 1
         return self.n_scalars - 1
 
     def allocate_point(self, label, enc):
+        if self.log is not None:
+            self.log["allocs"].append(["point", label.decode()])
         if enc == bytes(32):
             raise ProofError("identity point in the statement")      # validate_and_append_point_var
         _append_point(self.t, b"ptvar", label, enc)
@@ -83,6 +108,8 @@ class Verifier:
         return len(self.points) - 1
 
     def constrain(self, lhs, terms):
+        if self.log is not None:
+            self.log["constraints"].append([lhs, [[sv, pv] for sv, pv in terms]])
         self.constraints.append((lhs, list(terms)))
 
     def verify_compact(self, challenge, responses):

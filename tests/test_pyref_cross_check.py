@@ -125,8 +125,9 @@ def test_libsodium_recomputes_every_group_operation_of_every_flow(flows):
     negation that tests/pyref performs while replaying the golden flows - tags, messages, both provers' commitments, ciphertexts,
     Z, every commitment a verifier recomputes - is recomputed with libsodium's ristretto255 from the recorded scalars and point
     encodings.  With test_every_flow_replays_byte_for_byte (oracle == pyref on every byte) this pins the GROUP VALUES of the
-    flows to libsodium; what stays pinned only by the two restatements agreeing is the framing: transcript labels, the order of
-    allocations and constraints, which terms a constraint has.  libsodium exists in the build container only."""
+    flows to libsodium.  The framing - transcript labels, the order of allocations and constraints, which terms a constraint has -
+    is checked against text the reference holds (tests/test_framing.py, tests/golden/framing.json); what stays pinned only by the
+    two restatements agreeing is the inside of zkp, merlin and dalek as they restate it.  libsodium exists in the build container only."""
     from tests import sodium_replay
     sod = sodium_replay.load()
     if sod is None:
