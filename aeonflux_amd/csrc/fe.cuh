@@ -20,7 +20,8 @@
 // are limb-wise with no carry, so magnitudes add.  A product needs |f| * |g| <= 3.8 (column 7 holds 8 full products:
 // 8 * 3.8 * 2^58 plus the folds stays below 2^63), a squaring therefore |f| <= 1.9 (its doubled copy then fits int32).  ge.cuh states,
 // at each use, why the operands qualify; tests/test_device_arith_on_host.py runs the engine's chains on the host build of
-// this header with every column sum checked (AFX_CHECK_BOUNDS).  fe_carry() re-normalises to centred limbs.
+// this header with every column sum checked (AFX_CHECK_BOUNDS), and tests/test_gpu_device_arith.py runs the limit cases of that
+// test on the device build and compares the limbs with the host build's.  fe_carry() re-normalises to centred limbs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -6,7 +6,9 @@
 // 98).  A chain is 96 % squarings, everything else in the engine is mostly products: so the chains alone take this form, entered
 // and left through the canonical 32-byte encoding (fe_tobytes / fe_frombytes: ~1 % of a chain).
 // Bounds (checked on the actual operands by the host build, AFX_CHECK_BOUNDS): a raw result has limbs in [0, 2^26) / [0, 2^25)
-// (+ a carry on limb 1); it is valid as either operand of a product and as the input of a squaring - all a chain does.
+// (+ a carry of at most 19 * 2^11 + 1 on limb 1); it is valid as either operand of a product and as the input of a squaring - all a
+// chain does.  tests/test_device_arith_on_host.py probes that closure at the corners of the range on the host build,
+// tests/test_gpu_device_arith.py on the device build, limb for limb against the host build's.
 #pragma once
 
 struct fe10 {

@@ -65,7 +65,7 @@ AFX_DEV ge_p3 ge_p1p1_to_p3(const ge_p1p1& p) {
 //                a table entry of 1 unit.
 //   GE_FOR_ANY   everything centred (stores, encodings, table building, any other consumer).
 // tests/test_device_arith_on_host.py runs chains of these steps on the host build with every column sum checked
-// (AFX_CHECK_BOUNDS).
+// (AFX_CHECK_BOUNDS); tests/test_gpu_device_arith.py runs the point formulas at their exceptional inputs on the device build.
 enum { GE_FOR_DBL = 0, GE_FOR_ADD = 1, GE_FOR_ANY = 3 };
 template <int NEXT>
 AFX_DEV ge_p3 ge_p1p1_to_p3_for(const ge_p1p1& p) {

@@ -1,6 +1,7 @@
 // The engine's DEVICE arithmetic headers (fe.cuh, sc.cuh, ge.cuh), compiled for the host so that the CPU test-suite
 // can check them against the oracle without a GPU, and so that the field-operation counts DESIGN.md publishes are
-// measured rather than estimated.  Test infrastructure only: nothing in the product links this file.
+// measured rather than estimated.  Its device twin, tests/gpu_arith/arith_device.hip, runs the shared case bodies
+// (tests/gpu_arith/arith_cases.cuh) on the GPU.  Test infrastructure only: nothing in the product links this file.
 #include <stdint.h>
 #include <string.h>
 thread_local uint64_t afx_n_mul = 0, afx_n_sq = 0, afx_n_chain_mul = 0, afx_n_chain_sq = 0;
@@ -13,6 +14,7 @@ extern "C" void afx_bounds_violation(const char* what) { n_violations++; last_vi
 #include "../../aeonflux_amd/csrc/ge.cuh"
 #include "../../aeonflux_amd/csrc/sc.cuh"
 #include "../../aeonflux_amd/csrc/plan.h"
+#include "../gpu_arith/arith_cases.cuh"   // the case bodies this build shares with tests/gpu_arith/arith_device.hip
 
 static void load8(uint32_t w[8], const uint8_t* p) { memcpy(w, p, 32); }
 static sc sc_from(const uint8_t* p) { sc s; memcpy(s.v, p, 32); return s; }
@@ -33,7 +35,41 @@ uint64_t arith_bounds_checker_selftest(void) {
   n_violations = before;
   return caused;
 }
+// the same for fe10.cuh's checker: limbs of 2^28 (a 19-fold beyond int32, column sums beyond 2^62) as a product's operand and as
+// a squaring's
+uint64_t arith_bounds_checker_selftest10(void) {
+  const uint64_t before = n_violations;
+  fe10 big;
+  for (int i = 0; i < 10; i++) big.v[i] = 1 << 28;
+  (void)fe10_mul_raw(big, big);
+  (void)fe10_sq_raw(big);
+  const uint64_t caused = n_violations - before;
+  n_violations = before;
+  return caused;
+}
 const char* arith_last_violation(void) { return last_violation; }
+
+// The cases of tests/arith_cases.py, n of them, case-major words in and out (arith_cases.cuh): what the kernels of
+// tests/gpu_arith/arith_device.hip run one lane each, here in a loop with every product bound-checked.
+#define AC_HOST(name, body, NI, NO)                                      \
+  void name(const uint32_t* in, uint32_t* out, uint32_t n) {             \
+    for (uint32_t i = 0; i < n; i++) body(in + (size_t)i * NI, out + (size_t)i * NO); \
+  }
+AC_HOST(arith_host_fe_limbs, case_fe_limbs, AC_FE_LIMBS_IN, AC_FE_LIMBS_OUT)
+AC_HOST(arith_host_fe10_limbs, case_fe10_limbs, AC_FE10_LIMBS_IN, AC_FE10_LIMBS_OUT)
+AC_HOST(arith_host_fe_bytes, case_fe_bytes, AC_FE_BYTES_IN, AC_FE_BYTES_OUT)
+AC_HOST(arith_host_sqrt_ratio, case_sqrt_ratio, AC_SQRT_RATIO_IN, AC_SQRT_RATIO_OUT)
+AC_HOST(arith_host_elligator, case_elligator, AC_ELLIGATOR_IN, AC_ELLIGATOR_OUT)
+AC_HOST(arith_host_decode_encode, case_decode_encode, AC_DECODE_ENCODE_IN, AC_DECODE_ENCODE_OUT)
+AC_HOST(arith_host_point_ops, case_point_ops, AC_POINT_OPS_IN, AC_POINT_OPS_OUT)
+AC_HOST(arith_host_scalar, case_scalar, AC_SCALAR_IN, AC_SCALAR_OUT)
+// words per case of every kind, in the order of tests/arith_cases.py KINDS
+void arith_host_words(uint32_t out[16]) {
+  const uint32_t v[16] = { AC_FE_LIMBS_IN, AC_FE_LIMBS_OUT, AC_FE10_LIMBS_IN, AC_FE10_LIMBS_OUT, AC_FE_BYTES_IN, AC_FE_BYTES_OUT,
+                           AC_SQRT_RATIO_IN, AC_SQRT_RATIO_OUT, AC_ELLIGATOR_IN, AC_ELLIGATOR_OUT, AC_DECODE_ENCODE_IN, AC_DECODE_ENCODE_OUT,
+                           AC_POINT_OPS_IN, AC_POINT_OPS_OUT, AC_SCALAR_IN, AC_SCALAR_OUT };
+  for (int i = 0; i < 16; i++) out[i] = v[i];
+}
 
 // The doubling/addition chain of k_msm, step for step, with the same consumer-aware conversions (ge.cuh GE_FOR_*):
 // out = sum_t s[t] * P[t] (nv variable bases, signed 4-bit windows, per-"lane" tables as the kernel builds them)

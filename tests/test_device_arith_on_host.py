@@ -5,37 +5,21 @@ build measures the field-operation counts that DESIGN.md section 3 publishes."""
 import ctypes as C
 import hashlib
 import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-P = 2 ** 255 - 19
-L = 2 ** 252 + 27742317777372353535851937790883648493
+from tests import arith_cases
+from tests.arith_cases import L, P, ROOT, stream
 
 
 @pytest.fixture(scope="module")
 def arith(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("arith") / "libarith_host.so")
-    cmd = ["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-I" + os.path.join(ROOT, "tests", "hostsim", "include"), "-o", out,
-           os.path.join(ROOT, "tests", "hostsim", "arith_host.cpp")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    lib = C.CDLL(out)
-    lib.arith_bounds_violations.restype = C.c_uint64
-    lib.arith_last_violation.restype = C.c_char_p
-    return lib
-
-
-def stream(seed, n):
-    return hashlib.shake_256(seed).digest(n)
+    return arith_cases.build_host_lib(tmp_path_factory.mktemp("arith"))
 
 
 def test_field_ops_against_python_integers(arith):
-    s = stream(b"fe-host", 64 * 400)
-    edge = [bytes(32), (1).to_bytes(32, "little"), (P - 1).to_bytes(32, "little"), (P).to_bytes(32, "little"), b"\xff" * 32,
-            (2 ** 255 - 1).to_bytes(32, "little"), (2 ** 254).to_bytes(32, "little"), (19).to_bytes(32, "little")]
-    cases = [(s[64 * i:64 * i + 32], s[64 * i + 32:64 * i + 64]) for i in range(400)] + [(a, b) for a in edge for b in edge]
+    cases = arith_cases.field_byte_cases()
+    assert len(cases) == 400 + 64
     out = ((C.c_uint8 * 32) * 4)()
     for a, b in cases:
         arith.arith_fe(out, a, b)
@@ -59,39 +43,20 @@ def test_lazily_added_operands_at_the_documented_bounds(arith):
         assert int.from_bytes(bytes(out[1]), "little") == (v[0] - v[1]) ** 2 % P
 
 
-def _limbs_value(l):
-    return sum(int(x) << (29 * i) for i, x in enumerate(l))
+_limbs_value = arith_cases.limbs_value
 
 
 def test_products_at_the_limits_of_the_bounds_discipline(arith):
     """fe.cuh: a product needs |f| * |g| <= 3.8 units (1 unit = 2^29; limb 8: 2^23), a squaring |f| <= 1.9.  Operands with every limb at
     the extreme of its range, all sign patterns that maximise a column, must come out right and must not trip the checker."""
-    import random
-    rnd = random.Random(9)
-    unit = [1 << 29] * 8 + [1 << 23]
+    unit = arith_cases.UNIT
     out = ((C.c_uint8 * 32) * 5)()
     raw, cen = (C.c_int32 * 9)(), (C.c_int32 * 9)()
     before = arith.arith_bounds_violations()
-
-    def limbs(mag, mode):
-        v = []
-        for i in range(9):
-            top = int(unit[i] * mag) - 1
-            x = top if mode != "random" or rnd.random() < 0.5 else rnd.randrange(0, top + 1)
-            sign = {"pos": 1, "neg": -1, "alt": (-1) ** i, "random": rnd.choice((1, -1))}[mode]
-            v.append(sign * x)
-        return v
-    cases = []
-    for ma, mb in ((1, 1), (2, 1), (2, 1.9), (3.8, 1), (1, 3.8), (1.9, 1.99), (3, 1.25), (1.5, 2)):
-        for sa in ("pos", "neg", "alt", "random"):
-            for sb in ("pos", "neg", "alt", "random"):
-                cases.append((limbs(ma, sa), limbs(mb, sb)))
-    for _ in range(300):
-        ma = rnd.choice((1, 2, 3.8))
-        cases.append((limbs(ma, "random"), limbs(3.8 / ma if ma > 1 else 1, "random")))
+    cases = arith_cases.product_cases()           # shared with the device build: tests/test_gpu_device_arith.py
+    assert len(cases) == 428
     for f, g in cases:
-        # the squaring takes |f| <= 1.9: scale f down for it when the case is a wider operand
-        fs = f if max(abs(x) / u for x, u in zip(f, unit)) <= 1.9 else [x // 2 for x in f]
+        fs = arith_cases.squaring_operand(f)      # the squaring takes |f| <= 1.9
         arith.arith_fe_limbs(out, (C.c_int32 * 9)(*fs), (C.c_int32 * 9)(*g), 2 | 4)
         vs = _limbs_value(fs)
         assert int.from_bytes(bytes(out[2]), "little") == vs * vs % P and bytes(out[3]) == bytes(out[2])
@@ -111,11 +76,8 @@ def test_products_at_the_limits_of_the_bounds_discipline(arith):
 def test_canonical_encoding_of_edge_values(arith):
     """fe_tobytes on limb patterns around 0, p and 2^255, positive and negative, lazily added, up to the int32 range"""
     out = ((C.c_uint8 * 32) * 5)()
-    p_limbs = [(1 << 29) - 19] + [(1 << 29) - 1] * 7 + [(1 << 23) - 1]
-    vals = [[0] * 9, [1] + [0] * 8, [-1] + [0] * 8, [-19] + [0] * 8, [-20] + [0] * 8, p_limbs, [x + (i == 0) for i, x in enumerate(p_limbs)],
-            [x - (i == 0) for i, x in enumerate(p_limbs)], [-x for x in p_limbs], [2 * x for x in p_limbs], [-2 * x for x in p_limbs],
-            [(1 << 29) - 1] * 8 + [(1 << 23) - 1], [18] + [0] * 8, [19] + [0] * 8, [0] * 8 + [1 << 23], [0] * 8 + [-(1 << 23)],
-            [3 * x for x in p_limbs], [(1 << 31) - 1] * 9, [-(1 << 31)] * 9, [(-1) ** i * ((1 << 31) - 1) for i in range(9)]]
+    vals = arith_cases.encoding_limb_cases()
+    assert len(vals) == 20
     zero = (C.c_int32 * 9)(*([0] * 9))
     for v in vals:
         arith.arith_fe_limbs(out, (C.c_int32 * 9)(*v), zero, 4)
@@ -246,9 +208,37 @@ def test_negate_and_encode_against_the_oracle(arith, primitives):
     assert seen == {True, False} or len(pts) > 40   # 2-torsion-like fixed points are rare; most negations differ
 
 
+@pytest.mark.parametrize("kind", list(arith_cases.KINDS))
+def test_shared_limit_cases_on_the_host_build(arith, kind):
+    """the case list of tests/arith_cases.py - what tests/test_gpu_device_arith.py runs one lane each on the device build - through the
+    same case bodies (tests/gpu_arith/arith_cases.cuh) on this build: every result against Python integers, pyref or the oracle, the
+    limb ranges and the fe10 closure (arith_cases.check_*), and not one operand beyond the bounds discipline"""
+    got = (C.c_uint32 * 16)()
+    arith.arith_host_words(got)
+    assert list(got) == [x for k in arith_cases.KINDS.values() for x in k]
+    before = arith.arith_bounds_violations()
+    _, out = arith_cases.run(getattr(arith, "arith_host_" + kind), arith_cases.rows(kind), arith_cases.KINDS[kind][1])
+    arith_cases.check(kind, out)
+    assert arith.arith_bounds_violations() == before, arith.arith_last_violation()
+
+
+def test_device_harness_cross_compiles(tmp_path):
+    """tests/gpu_arith/arith_device.hip builds for gfx950 with the flags of the product's kernels.o (no GPU needed): the harness of
+    tests/test_gpu_device_arith.py cannot rot between GPU visits"""
+    cmd = arith_cases.device_compile_command(tmp_path / "libarith_device.so")
+    assert "-O3" in cmd and "--offload-arch=gfx950" in cmd and "-shared" in cmd
+    arith_cases.build_device_lib(tmp_path, load=False)
+    assert os.path.getsize(tmp_path / "libarith_device.so") > 0
+
+
 def test_the_bounds_checker_fires(arith):
     arith.arith_bounds_checker_selftest.restype = C.c_uint64
     assert arith.arith_bounds_checker_selftest() >= 2
+    # fe10.cuh's checker: an operand of 2^28 per limb trips it in the product and in the squaring, and the count is put back
+    arith.arith_bounds_checker_selftest10.restype = C.c_uint64
+    before = arith.arith_bounds_violations()
+    assert arith.arith_bounds_checker_selftest10() >= 2
+    assert arith.arith_bounds_violations() == before
 
 
 def test_no_bound_was_violated_anywhere(arith):
