@@ -224,6 +224,21 @@ def lib():
             _LIB.afx_keypairs_derive_dev.argtypes = _LIB.afx_keypairs_derive.argtypes
             _LIB.afx_encrypt_dev.argtypes = _LIB.afx_encrypt.argtypes
             _LIB.afx_decrypt_dev.argtypes = _LIB.afx_decrypt.argtypes
+        # (whole messages: any length, one key per message; offsets and chunk_first are host arrays in every form)
+        if hasattr(_LIB, "afx_encrypt_messages"):
+            _LIB.afx_message_chunks.restype = C.c_uint64
+            _LIB.afx_message_chunks.argtypes = [C.c_uint64]
+            _LIB.afx_messages_chunk_table.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+            _LIB.afx_plaintexts_from_messages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            _LIB.afx_plaintexts_from_messages_dev.argtypes = _LIB.afx_plaintexts_from_messages.argtypes + [C.c_void_p]
+            for sfx in ("", "_dev"):
+                getattr(_LIB, "afx_plaintexts_from_points" + sfx).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+                getattr(_LIB, "afx_plaintexts_from_bytes_at" + sfx).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                                C.c_void_p]
+                getattr(_LIB, "afx_encrypt_messages" + sfx).argtypes = [C.c_void_p, C.POINTER(KeypairsSoA), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                                        C.c_void_p, C.c_void_p]
+                getattr(_LIB, "afx_decrypt_messages" + sfx).argtypes = [C.c_void_p, C.POINTER(KeypairsSoA), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                                        C.c_void_p]
         # (blind issuance)
         if hasattr(_LIB, "afx_issue_blind"):
             for sfx in ("", "_dev"):

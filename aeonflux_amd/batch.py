@@ -414,6 +414,147 @@ def decrypt_dev(ctx, keypairs, E1, E2, count, M1, M2, m3, messages, status):
     check(lib().afx_decrypt_dev(ctx.h, C.byref(soa), _dptr(E1), _dptr(E2), count, _dptr(M1), _dptr(M2), _dptr(m3), _dptr(messages), _dptr(status)))
 
 
+# ---- whole messages (include/aeonflux_gpu.h "whole messages"): any length, one key per message ----
+def message_chunks(length):
+    """afx_message_chunks: 30-byte chunks of a message of `length` bytes"""
+    return int(lib().afx_message_chunks(length))
+
+
+def pack_messages(messages):
+    """a list of bytes -> (blob [total] u8, offsets [count + 1] u64); a (blob, offsets) pair goes through as arrays"""
+    if isinstance(messages, tuple):
+        blob, offsets = messages
+        return np.ascontiguousarray(np.frombuffer(bytes(blob), np.uint8) if isinstance(blob, (bytes, bytearray)) else _u8(blob).reshape(-1)), \
+            np.ascontiguousarray(offsets, dtype=np.uint64)
+    offsets = np.zeros(len(messages) + 1, np.uint64)
+    if len(messages):
+        offsets[1:] = np.cumsum([len(m) for m in messages], dtype=np.uint64)
+    return np.frombuffer(b"".join(bytes(m) for m in messages), np.uint8).copy(), offsets
+
+
+def chunk_table(offsets):
+    """afx_messages_chunk_table: offsets [count + 1] -> chunk_first [count + 1] u32"""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    cf = np.zeros(offsets.size, np.uint32)
+    check(lib().afx_messages_chunk_table(offsets.ctypes.data, offsets.size - 1, cf.ctypes.data))
+    return cf
+
+
+def _blob_ptr(blob):
+    # (a batch of only empty messages still hands the library a pointer)
+    return blob.ctypes.data if blob.size else _NO_BYTES.ctypes.data
+
+
+_NO_BYTES = np.zeros(16, np.uint8)
+
+
+def split_messages(rows, chunk_first):
+    """[n_chunks, 30] recovered rows -> a list of bytes, 30 * chunks(i) each"""
+    flat = _u8(rows).reshape(-1)
+    return [flat[30 * int(chunk_first[i]):30 * int(chunk_first[i + 1])].tobytes() for i in range(len(chunk_first) - 1)]
+
+
+def plaintexts_from_messages(ctx, messages):
+    """Plaintext::from_slice over a batch (afx_plaintexts_from_messages): messages = a list of bytes, or (blob, offsets)
+    -> M1, M2, m3 ([n_chunks, 32]), counters [n_chunks], chunk_first [count + 1]"""
+    blob, offsets = pack_messages(messages)
+    cf = chunk_table(offsets)
+    n = int(cf[-1])
+    M1, M2, m3 = (np.zeros((n, 32), np.uint8) for _ in range(3))
+    counters = np.zeros(n, np.uint32)
+    # (n == 0: numpy may hand out a null pointer for an empty array - the library gets room it will not write)
+    room = [np.zeros((1, 32), np.uint8) for _ in range(4)] if n == 0 else [M1, M2, m3, counters]
+    check(lib().afx_plaintexts_from_messages(ctx.h, _blob_ptr(blob), offsets.ctypes.data, offsets.size - 1, *(a.ctypes.data for a in room)))
+    return M1, M2, m3, counters, cf
+
+
+def plaintexts_from_points(ctx, points):
+    """impl From<&RistrettoPoint> for Plaintext (afx_plaintexts_from_points): points [count, 32] -> M2, m3 ([count, 32]), status [count]"""
+    points = _u8(points)
+    cnt = points.shape[0]
+    M2, m3 = np.zeros((cnt, 32), np.uint8), np.zeros((cnt, 32), np.uint8)
+    status = np.full(cnt, 255, np.uint8)
+    check(lib().afx_plaintexts_from_points(ctx.h, points.ctypes.data, cnt, M2.ctypes.data, m3.ctypes.data, status.ctypes.data))
+    return M2, m3, status
+
+
+def plaintexts_from_bytes_at(ctx, msgs, counters):
+    """afx_plaintexts_from_bytes_at: msgs [count, 30], counters [count] (what plaintexts_from_bytes returned) -> M1, M2, m3, status"""
+    msgs = _u8(msgs)
+    cnt = msgs.shape[0]
+    assert msgs.shape == (cnt, 30)
+    counters = np.ascontiguousarray(counters, dtype=np.uint32)
+    assert counters.shape == (cnt,)
+    M1, M2, m3 = (np.zeros((cnt, 32), np.uint8) for _ in range(3))
+    status = np.full(cnt, 255, np.uint8)
+    check(lib().afx_plaintexts_from_bytes_at(ctx.h, msgs.ctypes.data, counters.ctypes.data, cnt, M1.ctypes.data, M2.ctypes.data, m3.ctypes.data, status.ctypes.data))
+    return M1, M2, m3, status
+
+
+def encrypt_messages(ctx, keypairs, messages):
+    """afx_encrypt_messages: keypairs = dict(a, a0, a1[, pk]) with one row per MESSAGE; messages = a list of bytes, or (blob, offsets)
+    -> E1, E2 ([n_chunks, 32]), counters [n_chunks], chunk_first [count + 1], status [count] per message"""
+    kp = {f: _u8(v) for f, v in keypairs.items() if v is not None}
+    blob, offsets = pack_messages(messages)
+    cf = chunk_table(offsets)
+    cnt, n = offsets.size - 1, int(cf[-1])
+    assert kp["a"].shape == (cnt, 32)
+    E1, E2 = np.zeros((max(n, 1), 32), np.uint8), np.zeros((max(n, 1), 32), np.uint8)
+    counters = np.zeros(max(n, 1), np.uint32)
+    status = np.full(max(cnt, 1), 255, np.uint8)
+    soa = _keypairs_soa(kp, lambda a: a.ctypes.data)
+    check(lib().afx_encrypt_messages(ctx.h, C.byref(soa), _blob_ptr(blob), offsets.ctypes.data, cnt, E1.ctypes.data, E2.ctypes.data, counters.ctypes.data,
+                                     status.ctypes.data))
+    return E1[:n], E2[:n], counters[:n], cf, status[:cnt]
+
+
+def decrypt_messages(ctx, keypairs, E1, E2, chunk_first, fill=0, as_rows=False):
+    """afx_decrypt_messages: E1, E2 [n_chunks, 32], chunk_first [count + 1] -> (a list of bytes, 30 * chunks(i) each; status [count]).
+    A message that did not decrypt comes back as zeros.  `fill`: what the output holds before the call (tests); `as_rows`: the
+    [n_chunks, 30] array itself instead of the list (message i at row chunk_first[i])."""
+    kp = {f: _u8(v) for f, v in keypairs.items() if v is not None}
+    E1, E2 = _u8(E1), _u8(E2)
+    cf = np.ascontiguousarray(chunk_first, dtype=np.uint32)
+    cnt, n = cf.size - 1, int(cf[-1])
+    assert E1.shape[0] == n and E2.shape[0] == n
+    rows = np.full((max(n, 1), 30), fill, np.uint8)
+    status = np.full(max(cnt, 1), 255, np.uint8)
+    soa = _keypairs_soa(kp, lambda a: a.ctypes.data)
+    check(lib().afx_decrypt_messages(ctx.h, C.byref(soa), E1.ctypes.data if n else _NO_BYTES.ctypes.data, E2.ctypes.data if n else _NO_BYTES.ctypes.data,
+                                     cf.ctypes.data, cnt, rows.ctypes.data, status.ctypes.data))
+    return (rows[:n] if as_rows else split_messages(rows[:n], cf)), status[:cnt]
+
+
+# the *_dev forms: data pointers are device pointers; offsets / chunk_first stay host arrays (numpy), read before the call returns
+def plaintexts_from_messages_dev(ctx, blob, offsets, M1, M2, m3, counters, status):
+    """afx_plaintexts_from_messages_dev: blob on the device, offsets [count + 1] u64 on the host; status [n_chunks]"""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    check(lib().afx_plaintexts_from_messages_dev(ctx.h, _dptr(blob), offsets.ctypes.data, offsets.size - 1, _dptr(M1), _dptr(M2), _dptr(m3), _dptr(counters),
+                                                 _dptr(status)))
+
+
+def plaintexts_from_points_dev(ctx, points, count, M2, m3, status):
+    check(lib().afx_plaintexts_from_points_dev(ctx.h, _dptr(points), count, _dptr(M2), _dptr(m3), _dptr(status)))
+
+
+def plaintexts_from_bytes_at_dev(ctx, msgs, counters, count, M1, M2, m3, status):
+    check(lib().afx_plaintexts_from_bytes_at_dev(ctx.h, _dptr(msgs), _dptr(counters), count, _dptr(M1), _dptr(M2), _dptr(m3), _dptr(status)))
+
+
+def encrypt_messages_dev(ctx, keypairs, blob, offsets, E1, E2, counters, status):
+    """afx_encrypt_messages_dev: keypairs = dict(a, a0, a1) of device rows, one per message; status [count]"""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    soa = _keypairs_soa(keypairs, _dptr)
+    check(lib().afx_encrypt_messages_dev(ctx.h, C.byref(soa), _dptr(blob), offsets.ctypes.data, offsets.size - 1, _dptr(E1), _dptr(E2), _dptr(counters), _dptr(status)))
+
+
+def decrypt_messages_dev(ctx, keypairs, E1, E2, chunk_first, messages, status):
+    """afx_decrypt_messages_dev: chunk_first [count + 1] u32 on the host; messages [n_chunks][30] and status [count] on the device"""
+    cf = np.ascontiguousarray(chunk_first, dtype=np.uint32)
+    soa = _keypairs_soa(keypairs, _dptr)
+    check(lib().afx_decrypt_messages_dev(ctx.h, C.byref(soa), _dptr(E1), _dptr(E2), cf.ctypes.data, cf.size - 1, _dptr(messages), _dptr(status)))
+
+
 # ---- blind issuance (include/aeonflux_gpu.h "Blind issuance") ----
 REQUEST_FIELDS = ("D", "A", "B", "challenge", "responses")
 BLIND_ISSUANCE_FIELDS = ("t", "U", "S1", "S2", "challenge", "responses")

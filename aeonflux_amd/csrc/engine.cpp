@@ -17,6 +17,7 @@ hipError_t afxk_mask_rows(hipStream_t s, const afx_mask_job* jobs, uint32_t njob
 // (likewise: only the plaintext simulation, tests/hostsim/fake_plaintext.cpp, brings these two)
 hipError_t afxk_sha512_jobs(hipStream_t s, const afx_sha512_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
 hipError_t afxk_encode_to_group(hipStream_t s, const afx_encode_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
+hipError_t afxk_encode_at(hipStream_t s, const afx_encode_at_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
 
 namespace afx {
 namespace { size_t job_size(LaunchKind k); }   // bytes of one job of a launch kind (below, with the relocation)
@@ -987,6 +988,14 @@ void Assembler::encode_to_group(const afx_encode_job& job) {
   stats.chain_mul += 4 * AFX_CHAIN_SQRT_MUL; stats.chain_sq += 4 * AFX_CHAIN_SQRT_SQ;
   add_jobs(L_ENCODE, std::vector<afx_encode_job>(1, job));
 }
+void Assembler::encode_at(const afx_encode_at_job& job) {
+  flush_maps();
+  flush_encodings();   // (a failing item zeroes rows that queued encodings write: they go first)
+  stats.decodings += 1;
+  stats.field_mul += AFX_DECODE_MUL; stats.field_sq += AFX_DECODE_SQ;
+  stats.chain_mul += AFX_CHAIN_SQRT_MUL; stats.chain_sq += AFX_CHAIN_SQRT_SQ;
+  add_jobs(L_ENCODE_AT, std::vector<afx_encode_at_job>(1, job));
+}
 // rows of `count` dwords each: the opening launch's kernel (k_fill_u32) covers that many per grid row
 void Assembler::wipe(void* p, size_t bytes_per_item) {
   flush_maps();
@@ -1085,6 +1094,7 @@ size_t job_size(LaunchKind k) {
     case L_SHA512: return sizeof(afx_sha512_job);
     case L_ENCODE: return sizeof(afx_encode_job);
     case L_MASK: return sizeof(afx_mask_job);
+    case L_ENCODE_AT: return sizeof(afx_encode_at_job);
     default: return 0;
   }
 }
@@ -1152,6 +1162,7 @@ void Plan::relocate(uint8_t* nblob, uint8_t* nws, uint8_t* nin, uint8_t* nout) {
       case L_SHA512: for (uint32_t i = 0; i < l.njobs; i++) { afx_sha512_job& j = ((afx_sha512_job*)J)[i]; m.fix(j.src); m.fix(j.out); m.fix(j.copy); } break;
       case L_ENCODE: for (uint32_t i = 0; i < l.njobs; i++) { afx_encode_job& j = ((afx_encode_job*)J)[i]; m.fix(j.msgs); m.fix(j.M1); m.fix(j.counters); m.fix(j.zero_a); m.fix(j.zero_b); } break;
       case L_MASK: for (uint32_t i = 0; i < l.njobs; i++) m.fix(((afx_mask_job*)J)[i].p); break;
+      case L_ENCODE_AT: for (uint32_t i = 0; i < l.njobs; i++) { afx_encode_at_job& j = ((afx_encode_at_job*)J)[i]; m.fix(j.msgs); m.fix(j.counters_in); m.fix(j.M1); m.fix(j.zero_a); m.fix(j.zero_b); } break;
       case L_COPY: m.fix(l.in); m.fix(l.out); break;
       case L_KINDS: break;
     }
@@ -1378,6 +1389,10 @@ int run_plans(afx_ctx* ctx, int lane, Plan* const* plans, size_t n) {
       case L_MASK:
         if (!afxk_mask_rows) { set_error("no k_mask_rows launcher in this build"); return AFX_E_NO_DEVICE; }
         AFX_HIP(afxk_mask_rows(s, (const afx_mask_job*)jobs, nrows, rw, passes, max_count));
+        break;
+      case L_ENCODE_AT:
+        if (!afxk_encode_at) { set_error("no k_encode_at launcher in this build"); return AFX_E_NO_DEVICE; }
+        AFX_HIP(afxk_encode_at(s, (const afx_encode_at_job*)jobs, nrows, rw, passes, max_count));
         break;
       case L_MSM_TABLES: AFX_HIP(afxk_msm_tables(s, odd, (const afx_table_job*)jobs, nrows, rw, passes, max_count)); break;
       case L_MSM_FIXED: case L_MSM_WINDOW: case L_MSM_NAF: {

@@ -195,6 +195,10 @@ struct afx_ctx {
     void* pin_in = nullptr;          // pinned image of a SMALL call's whole staging area: its many short input rows are gathered
     size_t pin_in_cap = 0;           // here on the host and go to HBM in one copy (statements.hpp Stager::upload); wiped on destroy
     hipEvent_t pin_in_done = nullptr;   // end of the copy that last read pin_in
+    afx::DevBuf msg_ws;              // whole-message *_dev calls (statements_messages.cpp): chunk rows, per-chunk keys and plaintext rows, the two tables
+    void* msg_pin = nullptr;         // pinned image of the tables on their way to msg_ws (the host arrays are read before the call returns)
+    size_t msg_pin_cap = 0;
+    hipEvent_t msg_copied = nullptr;
     afx::DevBuf draw_jobs;           // the k_draw rows (and seed wipes) of the lane's latest device-drawn call (statements.hpp Stager::draw)
     afx::DevBuf weights;             // batchable verification: 256 bytes for the staged seed, then the call's weights [n_weights][count][16]
     void* weights_pin = nullptr;     // pinned image of the 40 seed bytes on their way to `weights` (zeroed once copied)
@@ -267,7 +271,7 @@ namespace afx {
 
 // L_MSM_WINDOW keeps the slot the single k_msm kernel had (timing names: statements.cpp KIND_NAMES)
 enum LaunchKind { L_FILL_BAD, L_DECODE, L_SCCHECK, L_POINTOP, L_SCALAROP, L_MSM_WINDOW, L_HASH, L_FROM_UNIFORM, L_REDUCE_WIDE, L_COPY, L_FINISH,
-                  L_MSM_FIXED, L_MSM_NAF, L_MSM_TABLES, L_COMPRESS, L_POINTSUM, L_NEGENC, L_TABLE_AFFINE, L_POWERS, L_COEF, L_SHA512, L_ENCODE, L_MASK, L_KINDS };
+                  L_MSM_FIXED, L_MSM_NAF, L_MSM_TABLES, L_COMPRESS, L_POINTSUM, L_NEGENC, L_TABLE_AFFINE, L_POWERS, L_COEF, L_SHA512, L_ENCODE, L_MASK, L_ENCODE_AT, L_KINDS };
 // Timing slots past the launch kinds: the two cooperative kernels an L_HASH launch may take instead of k_hash (kernels.hip
 // afxk_hash_coop), counted apart so that a test can say which kernel it ran.  "k_hash" (afx_ctx_get_timing) stays the three together.
 enum TimingSlot { T_HASH_COOP = L_KINDS, T_HASH_COOP64, T_SLOTS };
@@ -364,6 +368,7 @@ class Assembler {
   void reduce_wide(const uint8_t* wide, uint8_t* out);
   void sha512(const afx_sha512_job& job);             // out = SHA-512 of a byte range of every item's row (plan.h afx_sha512_job)
   void encode_to_group(const afx_encode_job& job);    // M1 = encode_to_group(msgs) (plan.h afx_encode_job); runs behind everything queued
+  void encode_at(const afx_encode_at_job& job);        // M1 = the candidate of msgs at counters_in, one decoding (plan.h afx_encode_at_job); runs behind everything queued
   void wipe(void* p, size_t bytes_per_item);          // zeroes a [count][bytes_per_item] array of the pass in stream order (a multiple of 4 bytes)
   void copy(uint8_t* dst, const uint8_t* src, size_t bytes);   // device-to-device
   void mask(const std::vector<uint8_t*>& rows);       // [count][32] output rows: the cells of items that have failed so far become zeros (k_mask_rows);

@@ -68,3 +68,10 @@ hipError_t afxk_sha512_jobs(hipStream_t s, const afx_sha512_job* jobs, uint32_t 
 hipError_t afxk_encode_to_group(hipStream_t s, const afx_encode_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count);
 // direct form (afx_sha512): out[i] = SHA-512(src + i * stride + offset, len), out [count][64]
 hipError_t afxk_sha512(hipStream_t s, const uint8_t* src, uint32_t stride, uint32_t offset, uint32_t len, uint8_t* out, uint32_t count);
+// the candidate at a known counter (plan.h afx_encode_at_job), a plan launch; and the three direct launches around the per-chunk plans
+// of the whole-message calls (plan.h afx_gather_job, afx_expand_job, afx_msgstat_job; messages.cuh): the job goes as the kernel
+// argument, its pointers are device pointers.  afxk_msg_status runs both phases.  Weak references on the host side, as above.
+hipError_t afxk_encode_at(hipStream_t s, const afx_encode_at_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count);
+hipError_t afxk_msg_gather(hipStream_t s, const afx_gather_job* job);
+hipError_t afxk_msg_expand(hipStream_t s, const afx_expand_job* job);
+hipError_t afxk_msg_status(hipStream_t s, const afx_msgstat_job* job);

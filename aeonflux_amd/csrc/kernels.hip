@@ -20,6 +20,7 @@
 //   k_from_uniform, k_reduce_wide   RistrettoPoint::from_uniform_bytes, Scalar::from_bytes_mod_order_wide
 //   k_sha512            SHA-512 of a byte range of every item's row (sha512.cuh): what turns application data into attributes
 //   k_encode_to_group   encoding.rs encode_to_group: the first counter whose candidate decodes
+//   k_encode_at, k_msg_gather, k_msg_expand, k_msg_status   messages.cuh: the candidate at a known counter; whole messages <-> chunk rows
 #include <hip/hip_runtime.h>
 #include "ge.cuh"
 #include "keccak.cuh"
@@ -2154,6 +2155,9 @@ hipError_t afxk_encode_to_group(hipStream_t s, const afx_encode_job* jobs, uint3
   hipLaunchKernelGGL(k_encode_to_group, grid_for(max_count, njobs), dim3(block_for(max_count)), 0, s, jobs, rows, passes);
   return hipGetLastError();
 }
+
+// whole messages: chunk gather, key-row expansion, per-message status and masking, the candidate at a known counter
+#include "messages.cuh"
 
 // the coefficient stage of the batchable presentation proofs: its two kernels and their launchers
 #include "batchable.cuh"

@@ -128,6 +128,36 @@ typedef struct { const uint8_t* src; uint8_t* out; uint8_t* copy; uint32_t strid
  * null) its counter.  An item none of whose 8192 candidates decodes fails (AFX_BAD_DECODE) and gets zeros in M1, its counter and its
  * rows of zero_a / zero_b (the call's other [count][32] outputs, or null). */
 typedef struct { const uint8_t* msgs; uint8_t* M1; uint32_t* counters; uint8_t* zero_a; uint8_t* zero_b; } afx_encode_job;
+/* k_encode_at, one lane per item: k_encode_to_group without its search - M1[item] = the candidate of msgs[item] at counters_in[item]
+ * (bytes[0] = 2 * (c mod 128), bytes[31] = c / 128), ONE decoding.  c >= 8192 or a candidate that does not decode fails the item
+ * (AFX_BAD_DECODE): zeros in M1 and in its rows of zero_a / zero_b. */
+typedef struct { const uint8_t* msgs; const uint32_t* counters_in; uint8_t* M1; uint8_t* zero_a; uint8_t* zero_b; } afx_encode_at_job;
+
+/* ---- whole messages (include/aeonflux_gpu.h "whole messages"): `count` messages as a byte blob + offsets[count + 1]; message i has
+ * (len_i + 29) / 30 chunks, which are rows chunk_first[i] .. chunk_first[i + 1] - 1 of every per-chunk array (chunk_first[count] =
+ * n_chunks).  The three kernels below are launched directly with their job as the kernel argument, one lane per chunk; each finds its
+ * chunk's message by a binary search in chunk_first (public lengths only; neighbouring lanes read the same entries). */
+/* k_msg_gather: rows[chunk] = the chunk's 30 bytes of its message, zero-padded ([n_chunks][30]; byte loads and stores: neither the
+ * blob nor a 30-byte row promises alignment).  `blob` points at byte `bias` of the caller's blob (a host-pointer call stages the
+ * bytes from offsets[0] on). */
+typedef struct { const uint8_t* blob; const uint64_t* offsets; const uint32_t* chunk_first; uint8_t* rows; uint64_t bias; uint32_t count, n_chunks; } afx_gather_job;
+/* k_msg_expand: dst[k][chunk] = src[k][message of chunk], 32-byte rows (16-byte aligned), k < n_rows: a message's key scalars for
+ * each of its chunks */
+#define AFX_EXPAND_MAX 3
+typedef struct { const uint8_t* src[AFX_EXPAND_MAX]; uint8_t* dst[AFX_EXPAND_MAX]; const uint32_t* chunk_first; uint32_t count, n_chunks, n_rows; } afx_expand_job;
+/* k_msg_status, two launches behind the LAST pass of the per-chunk plan (a message's chunks may lie in several passes):
+ *   phase 0, lanes 0 .. max(n_chunks, count): status[message of chunk] = fail_code where chunk_status[0 or 1][chunk] != 0 (the second may be null; plain byte stores of
+ *            one value - no atomics; `status` was zeroed before); lane i < count also fails message i for a non-canonical scalar in
+ *            keys[k][i] (k < n_keys; or none)
+ *   phase 1, a lane per chunk: the chunk's row in rows32[0..1] ([n_chunks][32]), rows30 ([n_chunks][30]) and words ([n_chunks] u32)
+ *            - those that are not null - becomes zeros where the chunk's message has failed */
+typedef struct {
+  const uint8_t* chunk_status[2]; uint8_t* status; const uint32_t* chunk_first;
+  const uint8_t* keys[AFX_EXPAND_MAX];
+  uint8_t* rows32[2]; uint8_t* rows30; uint32_t* words;
+  uint32_t count, n_chunks, n_keys, fail_code, phase, pad;
+} afx_msgstat_job;
+
 /* k_draw, one grid row per job: item i of the row gets draw(seed, stream, index + i, label) (keccak.cuh shake256_draw), AFX_DRAW_LEN(label)
  * bytes at dst + i * AFX_DRAW_LEN(label).  `seed`: the call's 40 staged bytes seed || u64le(stream), 8-byte aligned; dst 16-byte aligned. */
 typedef struct { const uint8_t* seed; uint8_t* dst; uint64_t index; uint32_t count, label; } afx_draw_job;

@@ -39,7 +39,7 @@ extern "C" void* afx_ctx_stream(const afx_ctx* ctx) { return ctx ? (void*)ctx->s
 // indexed by afx::LaunchKind, then afx::TimingSlot.  "k_msm" (afx_ctx_get_timing) = the three chain kernels + the table kernel together;
 // "k_hash" = the one-lane kernel + the two cooperative ones together (the slot L_HASH itself holds the one-lane kernel alone)
 static const char* const KIND_NAMES[] = { "k_fill_u32", "k_decode", "k_sccheck", "k_pointop", "k_scalarop", "k_msm_window", "k_hash",
-                                          "k_from_uniform", "k_reduce_wide", "copy", "k_finish", "k_msm_fixed", "k_msm_naf", "k_msm_tables", "k_compress2x", "k_pointsum", "k_negenc", "k_table_affine", "k_powers", "k_coef", "k_sha512", "k_encode_to_group", "k_mask_rows",
+                                          "k_from_uniform", "k_reduce_wide", "copy", "k_finish", "k_msm_fixed", "k_msm_naf", "k_msm_tables", "k_compress2x", "k_pointsum", "k_negenc", "k_table_affine", "k_powers", "k_coef", "k_sha512", "k_encode_to_group", "k_mask_rows", "k_encode_at",
                                           "k_hash_coop", "k_hash_coop64" };
 static_assert(sizeof KIND_NAMES / sizeof KIND_NAMES[0] == afx::T_SLOTS, "one name per launch kind and timing slot");
 static int drain_timing(afx_ctx* c) {
@@ -269,6 +269,9 @@ extern "C" void afx_ctx_destroy(afx_ctx* c) {
     L.staging.release(true);
     L.staging_out.release(true);
     L.draw_jobs.release(true);
+    L.msg_ws.release(true);
+    if (L.msg_pin) { memset(L.msg_pin, 0, L.msg_pin_cap); (void)hipHostFree(L.msg_pin); L.msg_pin = nullptr; L.msg_pin_cap = 0; }
+    if (L.msg_copied) { (void)hipEventDestroy(L.msg_copied); L.msg_copied = nullptr; }
     L.weights.release(true);
     if (L.weights_pin) { memset(L.weights_pin, 0, 64); (void)hipHostFree(L.weights_pin); L.weights_pin = nullptr; }
     if (L.weights_copied) { (void)hipEventDestroy(L.weights_copied); L.weights_copied = nullptr; }

@@ -242,6 +242,14 @@ struct CtxLock {
 // and reused by later calls of the same statement, shape, mode and (padded) size - those only copy it and move its pointers.
 int run_chunked(afx_ctx* c, size_t count, const BuildFn& build, const PlanKey& key = PlanKey());
 
+// statements_setup.cpp: the plans of afx_plaintexts_from_bytes_dev, afx_encrypt_dev and afx_decrypt_dev over device rows - what the
+// whole-message calls (statements_messages.cpp) run on the chunk rows they gather
+int plaintexts_on_device(afx_ctx* ctx, const uint8_t* msgs, size_t count, uint8_t* M1, uint8_t* M2, uint8_t* m3, uint32_t* counters, uint8_t* status);
+int encrypt_on_device(afx_ctx* ctx, const uint8_t* a, const uint8_t* a0, const uint8_t* a1, const uint8_t* M1, const uint8_t* M2, const uint8_t* m3, size_t count,
+                      uint8_t* E1, uint8_t* E2, uint8_t* status);
+int decrypt_on_device(afx_ctx* ctx, const uint8_t* a, const uint8_t* a0, const uint8_t* a1, const uint8_t* E1, const uint8_t* E2, size_t count, uint8_t* M1,
+                      uint8_t* M2, uint8_t* m3, uint8_t* messages, uint8_t* status);
+
 struct JobSets {
   std::vector<afx_sccheck_job> sccheck;
   std::vector<afx_decode_job> decode;

@@ -212,7 +212,7 @@ static int derive_without_hash_kernels(afx_ctx* ctx, const uint8_t* master_secre
 }
 
 // Keypair::encrypt over device rows: E1 = (a0 + a1*m3)*M2, E2 = a*E1 + M1  (symmetric.rs:252-261)
-static int encrypt_on_device(afx_ctx* ctx, const uint8_t* a, const uint8_t* a0, const uint8_t* a1, const uint8_t* M1, const uint8_t* M2, const uint8_t* m3, size_t count,
+int encrypt_on_device(afx_ctx* ctx, const uint8_t* a, const uint8_t* a0, const uint8_t* a1, const uint8_t* M1, const uint8_t* M2, const uint8_t* m3, size_t count,
                              uint8_t* E1, uint8_t* E2, uint8_t* status) {
   return run_chunked(ctx, count, [&](Assembler& as, size_t off, uint32_t) {
     as.secret_scalars = true;   // the user's symmetric key: afx_ctx_set_secret_independent_addressing
@@ -323,9 +323,10 @@ static afx_sha512_job mk_sha(const uint8_t* src, uint32_t stride, uint32_t offse
   return j;
 }
 
+// (the three plans over rows are also what the whole-message calls run on their chunk rows: statements.hpp, statements_messages.cpp)
 // impl From<&[u8; 30]> for Plaintext (symmetric.rs:135-143): wide = SHA-512(m); M2 = from_uniform_bytes(wide), m3 = wide mod l;
 // M1 = encode_to_group(m)
-static int plaintexts_on_device(afx_ctx* ctx, const uint8_t* msgs, size_t count, uint8_t* M1, uint8_t* M2, uint8_t* m3, uint32_t* counters, uint8_t* status) {
+int plaintexts_on_device(afx_ctx* ctx, const uint8_t* msgs, size_t count, uint8_t* M1, uint8_t* M2, uint8_t* m3, uint32_t* counters, uint8_t* status) {
   return run_chunked(ctx, count, [&](Assembler& as, size_t off, uint32_t) {
     uint8_t* wide = as.new_wide();
     as.sha512(mk_sha(msgs + 30 * off, 30, 0, 30, wide));
@@ -417,7 +418,7 @@ extern "C" int afx_keypairs_derive(afx_ctx* ctx, const uint8_t* master_secrets, 
 // Keypair::decrypt (symmetric.rs:273-289): M1' = E2 - a*E1; m' = bytes 1..30 of its encoding (decode_from_group, encoding.rs:75-82);
 // wide = SHA-512(m'), m3' = wide mod l, M2' = from_uniform_bytes(wide); E1' = (a0 + a1*m3')*M2'; the item decrypts iff E1 - E1' is the
 // identity
-static int decrypt_on_device(afx_ctx* ctx, const uint8_t* a, const uint8_t* a0, const uint8_t* a1, const uint8_t* E1, const uint8_t* E2, size_t count, uint8_t* M1,
+int decrypt_on_device(afx_ctx* ctx, const uint8_t* a, const uint8_t* a0, const uint8_t* a1, const uint8_t* E1, const uint8_t* E2, size_t count, uint8_t* M1,
                              uint8_t* M2, uint8_t* m3, uint8_t* messages, uint8_t* status) {
   return run_chunked(ctx, count, [&](Assembler& as, size_t off, uint32_t) {
     as.secret_scalars = true;   // the user's symmetric key: afx_ctx_set_secret_independent_addressing

@@ -1162,6 +1162,78 @@ int afx_decrypt_dev(afx_ctx* ctx, const afx_keypairs_soa* keypairs, const uint8_
  * four calls above hash with, as a batch primitive - published vectors run on the device.  Host pointers. */
 int afx_sha512(afx_ctx* ctx, const uint8_t* msgs /*[count][msg_len]*/, size_t msg_len, size_t count, uint8_t* out /*[count][64]*/);
 
+/* ---- whole messages: any length, one key per message -----------------------------------------
+ * The request constructor of the crate takes application data of any length: CredentialRequestConstructor::append_plaintext
+ * (src/user.rs:69-77) calls Plaintext::from_slice (src/symmetric.rs:118-133), which cuts the message into 30-byte chunks
+ * (`chunks(30)`: the doc comment's "31-byte segments" is not what the code does), zero-pads the last one and makes one Plaintext per
+ * chunk.  These calls do the same for a batch, and encrypt and decrypt whole messages under one key each.  Off unless called: no
+ * existing call, plan or kernel changes.
+ *
+ * A batch of `count` messages is a byte `blob` and offsets[count + 1] (non-decreasing); message i is blob[offsets[i] .. offsets[i+1]).
+ *  - Message i has chunks(i) = (len_i + 29) / 30 chunks.  An empty message has none, as slice.chunks(30) yields none.
+ *  - chunk_first[i] is the sum of the earlier messages' chunk counts; n_chunks = chunk_first[count].
+ *  - Chunk k of message i is row chunk_first[i] + k of every per-chunk array.  Its 30 bytes are the message's bytes 30k .. 30k + 29,
+ *    zero-padded.
+ *  - The length is not carried: b"abc" and b"abc\0" give the same rows, as in the crate.  A recovered message has 30 * chunks(i) bytes.
+ * offsets and chunk_first are HOST arrays in every form, the *_dev forms included: they size the plan and are read before the call
+ * returns.  Malformed input - decreasing offsets, a chunk_first that does not start at 0 or decreases, more than 2^32 - 1 chunks - is
+ * AFX_E_BAD_ARGS and nothing is written.
+ * In the *_dev forms the data pointers are device pointers, rows are 16-byte aligned (counters 4-byte), the blob has any alignment, and
+ * the call is asynchronous on afx_ctx_stream.  The host-pointer forms stage the blob, the two tables and the keys (one row per
+ * MESSAGE) once and fetch once.  Chunk rows beyond afx_ctx_set_chunk_items run as several passes, cut wherever that falls: a message's
+ * chunks may lie in several passes, and what is decided per message is decided behind the last one.
+ *
+ * Secrets: the per-chunk copies of a, a0, a1, the hashes of recovered chunks, a0 + a1*m3' and the per-chunk M1', M2', m3' are zeroed on
+ * the device, in stream order, before the call completes.  The encrypting and decrypting plans are afx_encrypt's and afx_decrypt's and
+ * run under the context's secret-independent addressing.  The chunk -> message map depends on the public lengths only. */
+
+/* (len + 29) / 30, for any len (no overflow).  Host only, no context. */
+uint64_t afx_message_chunks(uint64_t len);
+/* chunk_first_out[0 .. count] from offsets[0 .. count].  Host only, no context.  AFX_E_BAD_ARGS, nothing written: a NULL argument,
+ * decreasing offsets, more than 2^32 - 1 chunks. */
+int afx_messages_chunk_table(const uint64_t* offsets, size_t count, uint32_t* chunk_first_out /* [count + 1] */);
+
+/* Plaintext::from_slice over a batch: M1, M2, m3 [n_chunks][32], counters [n_chunks] or NULL.  Row for row what
+ * afx_plaintexts_from_bytes gives on the padded chunks, with its failure contract: the host form returns AFX_E_BAD_ARGS, the _dev form
+ * gives a status per CHUNK (status [n_chunks]) and zeroed rows. */
+int afx_plaintexts_from_messages(afx_ctx* ctx, const uint8_t* blob, const uint64_t* offsets, size_t count, uint8_t* M1, uint8_t* M2, uint8_t* m3,
+                                 uint32_t* counters /* or NULL */);
+int afx_plaintexts_from_messages_dev(afx_ctx* ctx, const uint8_t* blob, const uint64_t* offsets /* host */, size_t count, uint8_t* M1, uint8_t* M2,
+                                     uint8_t* m3, uint32_t* counters /* or NULL */, uint8_t* status /* [n_chunks] */);
+/* impl From<&RistrettoPoint> for Plaintext (src/symmetric.rs:152-161) - how a user rebuilds M2 and m3 of a point attribute held only as
+ * a point: wide = SHA-512(the 32 bytes), M2 = from_uniform_bytes(wide), m3 = wide mod l.  points [count][32]; M2, m3 [count][32].  An
+ * encoding that does not decode gets AFX_ST_VERIFICATION_FAILURE and zero rows; the identity is a valid input.  A ristretto encoding
+ * that decodes is canonical, so the bytes hashed are the bytes given.  (This is NOT the triple afx_plaintexts_from_bytes gives for the
+ * message a point encodes: the crate hashes different bytes.) */
+int afx_plaintexts_from_points(afx_ctx* ctx, const uint8_t* points, size_t count, uint8_t* M2, uint8_t* m3, uint8_t* status);
+int afx_plaintexts_from_points_dev(afx_ctx* ctx, const uint8_t* points, size_t count, uint8_t* M2, uint8_t* m3, uint8_t* status);
+/* afx_plaintexts_from_bytes for a caller that kept the counters it returned ("XXX shortcut if counter is known", src/encoding.rs:54):
+ * msgs [count][30], counters_in [count].  M1 is the candidate at counters_in[i] (bytes[0] = 2 * (c mod 128), bytes[31] = c / 128): ONE
+ * decoding, no search.  c >= 8192, or a candidate that does not decode, gets AFX_ST_VERIFICATION_FAILURE and zero rows (M1, M2, m3).
+ * The result equals afx_plaintexts_from_bytes' result if and only if c is the counter that call returns.  Any other accepted c gives
+ * ANOTHER M1, which decode_from_group maps to the same 30 bytes (M2 and m3 do not depend on c). */
+int afx_plaintexts_from_bytes_at(afx_ctx* ctx, const uint8_t* msgs, const uint32_t* counters_in, size_t count, uint8_t* M1, uint8_t* M2, uint8_t* m3,
+                                 uint8_t* status);
+int afx_plaintexts_from_bytes_at_dev(afx_ctx* ctx, const uint8_t* msgs, const uint32_t* counters_in, size_t count, uint8_t* M1, uint8_t* M2, uint8_t* m3,
+                                     uint8_t* status);
+/* Keypair::encrypt of every chunk of every message under the MESSAGE's key: keypairs->a, a0, a1 [count][32] (pk is not read);
+ * E1, E2 [n_chunks][32], counters [n_chunks] or NULL, status [count] per MESSAGE.  Per chunk it is afx_encrypt of
+ * afx_plaintexts_from_bytes.  A message fails as a whole - AFX_ST_VERIFICATION_FAILURE, zeros in all its E1 / E2 rows (and counters) -
+ * if its key has a non-canonical scalar or any of its chunks fails.  A message of zero chunks writes no row. */
+int afx_encrypt_messages(afx_ctx* ctx, const afx_keypairs_soa* keypairs, const uint8_t* blob, const uint64_t* offsets, size_t count, uint8_t* E1,
+                         uint8_t* E2, uint32_t* counters /* or NULL */, uint8_t* status);
+int afx_encrypt_messages_dev(afx_ctx* ctx, const afx_keypairs_soa* keypairs, const uint8_t* blob, const uint64_t* offsets /* host */, size_t count,
+                             uint8_t* E1, uint8_t* E2, uint32_t* counters /* or NULL */, uint8_t* status);
+/* Keypair::decrypt of every chunk (afx_decrypt) under the message's key: E1, E2 [n_chunks][32], chunk_first [count + 1] (host;
+ * afx_messages_chunk_table), messages [n_chunks][30] - message i's 30 * chunks(i) bytes at 30 * chunk_first[i] - status [count].
+ * A message is AFX_ST_UNDECRYPTABLE iff any of its chunks is, and ALL its 30 * chunks(i) bytes are then zeros, written on the device
+ * before the call completes: nothing is released of a message that was not accepted (the rule of the blind calls' outputs), the chunks
+ * that by themselves decrypted included.  A neighbour's bytes are untouched.  A message of zero chunks is AFX_ST_OK. */
+int afx_decrypt_messages(afx_ctx* ctx, const afx_keypairs_soa* keypairs, const uint8_t* E1, const uint8_t* E2, const uint32_t* chunk_first, size_t count,
+                         uint8_t* messages, uint8_t* status);
+int afx_decrypt_messages_dev(afx_ctx* ctx, const afx_keypairs_soa* keypairs, const uint8_t* E1, const uint8_t* E2, const uint32_t* chunk_first /* host */,
+                             size_t count, uint8_t* messages, uint8_t* status);
+
 /* Batch ristretto255 primitives (dalek CompressedRistretto::decompress -> compress round trip,
  * RistrettoPoint::from_uniform_bytes, Scalar::from_bytes_mod_order_wide); used to build synthetic
  * attribute values and by the parity tests of the K* rows. */
