@@ -9,18 +9,7 @@
 #include <system_error>
 #include <stdexcept>
 
-// (a weak reference, like afxk_draw in plans.cpp: the host simulation builds of the engine link the launchers they need from
-// tests/hostsim, and only the batchable simulation brings this one)
-hipError_t afxk_coef(hipStream_t s, const afx_coef_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
-// (likewise: only the blind-issuance simulation, tests/hostsim/fake_blind.cpp, brings this one)
-hipError_t afxk_mask_rows(hipStream_t s, const afx_mask_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
-// (likewise: only the plaintext simulation, tests/hostsim/fake_plaintext.cpp, brings these two)
-hipError_t afxk_sha512_jobs(hipStream_t s, const afx_sha512_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
-hipError_t afxk_encode_to_group(hipStream_t s, const afx_encode_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
-hipError_t afxk_encode_at(hipStream_t s, const afx_encode_at_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
-
 namespace afx {
-namespace { size_t job_size(LaunchKind k); }   // bytes of one job of a launch kind (below, with the relocation)
 
 static thread_local std::string g_error;
 void set_error(const std::string& s) { g_error = s; }
@@ -132,11 +121,12 @@ template <> void put_job(uint8_t* dst, const afx_scalarop_job& j) {
   z.a = j.a; z.a_stride = j.a_stride; z.b = j.b; z.b_stride = j.b_stride; z.c = j.c; z.c_stride = j.c_stride; z.negate = j.negate; z.out = j.out;
   memcpy(dst, &z, sizeof z);
 }
-template <class T>
-void Assembler::add_jobs(LaunchKind k, const std::vector<T>& jobs) {
+template <LaunchKind K, class T>
+void Assembler::add_jobs(const std::vector<T>& jobs) {
+  static_assert(job_of_kind<T>(K), "not the job struct of this launch kind");
   if (jobs.empty()) return;
   Launch l;
-  l.kind = k;
+  l.kind = K;
   l.njobs = (uint32_t)jobs.size();
   l.jobs_off = blob_alloc(sizeof(T) * jobs.size(), 16);
   for (size_t i = 0; i < jobs.size(); i++) put_job(blob_.data() + l.jobs_off + sizeof(T) * i, jobs[i]);
@@ -153,19 +143,19 @@ void Assembler::decode(const std::vector<afx_decode_job>& jobs) {
     std::vector<afx_decode_job> all(pending_maps_);
     all.insert(all.end(), jobs.begin(), jobs.end());
     pending_maps_.clear();
-    add_jobs(L_DECODE, all);
+    add_jobs(all);
     launches.back().odd = 1;
     flush_maps();
     return;
   }
-  add_jobs(L_DECODE, jobs);
+  add_jobs(jobs);
 }
 // what from_uniform queued and no decode() call took along: a launch of its own, then the sums
 void Assembler::flush_maps() {
   if (!pending_maps_.empty()) {
     std::vector<afx_decode_job> maps;
     maps.swap(pending_maps_);
-    add_jobs(L_DECODE, maps);
+    add_jobs(maps);
     launches.back().odd = 1;
   }
   if (!pending_map_sums_.empty()) {
@@ -174,7 +164,7 @@ void Assembler::flush_maps() {
     pointop(sums);
   }
 }
-void Assembler::sccheck(const std::vector<afx_sccheck_job>& jobs) { add_jobs(L_SCCHECK, jobs); }
+void Assembler::sccheck(const std::vector<afx_sccheck_job>& jobs) { add_jobs(jobs); }
 void Assembler::pointop(const std::vector<afx_pointop_job>& jobs) {
   flush_maps();
   for (const afx_pointop_job& j : jobs) {
@@ -197,10 +187,10 @@ void Assembler::pointop(const std::vector<afx_pointop_job>& jobs) {
       pending_cjobs_.push_back(cj);
       j.out_enc = nullptr; j.reject_identity = 0;
     }
-    add_jobs(L_POINTOP, moved);
+    add_jobs(moved);
     return;
   }
-  add_jobs(L_POINTOP, jobs);
+  add_jobs(jobs);
 }
 void Assembler::negenc(const std::vector<afx_negenc_job>& jobs) {
   flush_maps();
@@ -209,7 +199,7 @@ void Assembler::negenc(const std::vector<afx_negenc_job>& jobs) {
   stats.field_mul += 11 + (2 * 3 + 2 + 17) * jobs.size();   // one inversion; per point: the value to invert twice, prefix products, the encoding's tail
   stats.field_sq += 254 + 3 * jobs.size();
   stats.chain_mul += AFX_CHAIN_INVERT_MUL; stats.chain_sq += AFX_CHAIN_INVERT_SQ;
-  add_jobs(L_NEGENC, jobs);
+  add_jobs(jobs);
   add_walk_rows(launches.back(), 0);
 }
 // grid rows of a k_compress2x / k_negenc / k_table_affine launch: per_row jobs each (0 = all in one row), each row with scratch for
@@ -220,7 +210,7 @@ void Assembler::add_walk_rows(Launch& l, uint32_t per_row) {
   for (uint32_t first = 0; first < l.njobs; first += per_row) {
     afx_walk_row r;
     memset(&r, 0, sizeof r);
-    r.job_off = first * (uint32_t)job_size(l.kind);
+    r.job_off = first * (uint32_t)kind_info(l.kind).job_size;
     r.n_jobs = std::min(per_row, l.njobs - first);
     r.pass = 0;
     r.prefix_ws = l.kind == L_TABLE_AFFINE ? nullptr : (int32_t*)ws_alloc(sizeof(int32_t) * 9 * (size_t)r.n_jobs * (size_t)count);
@@ -230,17 +220,17 @@ void Assembler::add_walk_rows(Launch& l, uint32_t per_row) {
   l.rows_off = blob_alloc(sizeof(afx_walk_row) * rows.size(), 16);
   memcpy(blob_.data() + l.rows_off, rows.data(), sizeof(afx_walk_row) * rows.size());
 }
-void Assembler::scalarop(const std::vector<afx_scalarop_job>& jobs) { flush_maps(); add_jobs(L_SCALAROP, jobs); }
-void Assembler::coef(const std::vector<afx_coef_job>& jobs) { flush_maps(); add_jobs(L_COEF, jobs); }
+void Assembler::scalarop(const std::vector<afx_scalarop_job>& jobs) { flush_maps(); add_jobs(jobs); }
+void Assembler::coef(const std::vector<afx_coef_job>& jobs) { flush_maps(); add_jobs(jobs); }
 void Assembler::hash(const std::vector<afx_hash_program>& progs) {
   flush_maps();
   flush_encodings();   // encodings still queued (Assembler::pointop, compress_also, a small pass's stages) are launched before their reader
   for (const afx_hash_program& p : progs) stats.keccak_permutations += p.n_records;
-  add_jobs(L_HASH, progs);
+  add_jobs(progs);
   if (!pending_reductions_.empty()) {   // the blindings these transcripts squeezed out unreduced (SchnorrBuilder::prove_compact, small passes)
     std::vector<afx_reduce_job> rj;
     rj.swap(pending_reductions_);
-    add_jobs(L_REDUCE_WIDE, rj);
+    add_jobs(rj);
   }
 }
 // Width-5 NAF of a canonical scalar (little-endian 32 bytes): digits in {0, +-1, +-3, ..., +-15}, at most one
@@ -358,13 +348,9 @@ static std::vector<size_t> balanced_row_order(const std::vector<size_t>& heads, 
 // k_compress2x over `cjobs`, in `groups` grid rows: each row walks its share of an item's jobs with one field inversion
 void Assembler::compress(const std::vector<afx_compress_job>& cjobs, uint32_t groups) {
   if (cjobs.empty()) return;
-  Launch cl;
-  cl.kind = L_COMPRESS;
-  cl.njobs = (uint32_t)cjobs.size();
-  cl.jobs_off = blob_alloc(sizeof(afx_compress_job) * cjobs.size(), 16);
-  memcpy(blob_.data() + cl.jobs_off, cjobs.data(), sizeof(afx_compress_job) * cjobs.size());
+  add_jobs(cjobs);
+  Launch& cl = launches.back();
   add_walk_rows(cl, groups > 1 ? (cl.njobs + groups - 1) / groups : 0);
-  launches.push_back(cl);
   // the plain encodings were counted job by job: replace them by k_compress2x's share (two passes over e, f, g, h per job, one
   // inversion per row)
   // (plain jobs - points encoded as they are, moved here by Assembler::pointop - keep the share they were counted with)
@@ -528,7 +514,7 @@ bool Assembler::segment_bases(const std::vector<afx_msm_job>& jobs) {
       const uint64_t d = (uint64_t)q.step * q.n_out;   // doublings: four squarings, four products each (kernels.hip quad_dbl)
       stats.doublings += d; stats.field_sq += 4 * d; stats.field_mul += 4 * d;
     }
-  if (!pj.empty()) add_jobs(L_POWERS, pj);
+  if (!pj.empty()) add_jobs(pj);
   if (any && secret_scalars) segmenting_ = true;   // (a prover's pass has later stages on the same bases: its narrow tables stay)
   return any;
 }
@@ -638,7 +624,7 @@ void Assembler::msm_split(std::vector<afx_msm_job> jobs, std::vector<afx_compres
       sums.push_back(sj);
     }
     msm_list(std::move(subs), no_naf, cjobs);
-    add_jobs(L_POINTSUM, sums);
+    add_jobs(sums);
     if (!sums.empty())   // (Launch::odd of a sum: some job has sixteen parts or more - kernels.hip afxk_pointsum)
       for (const afx_pointsum_job& sj : sums) if (sj.n_parts >= 16) launches.back().odd = 1;
   }
@@ -797,22 +783,13 @@ void Assembler::msm_list(std::vector<afx_msm_job> jobs, bool no_naf, std::vector
   // the narrow tables of `tr`: built (k_msm_tables, kind 2) and made affine - one inversion per item and grid row over all of the
   // launch's tables (kernels.hip k_table_affine); a small pass, which waits for the serial walk, spreads them over up to 8 rows
   auto emit_narrow_tables = [&](const std::vector<afx_table_job>& tr) {
-    Launch tl;
-    tl.kind = L_MSM_TABLES;
-    tl.odd = cached_narrow ? 3 : 2;
-    tl.njobs = (uint32_t)tr.size();
-    tl.jobs_off = blob_alloc(sizeof(afx_table_job) * tr.size(), 16);
-    memcpy(blob_.data() + tl.jobs_off, tr.data(), sizeof(afx_table_job) * tr.size());
-    launches.push_back(tl);
+    add_jobs<L_MSM_TABLES>(tr);
+    launches.back().odd = cached_narrow ? 3 : 2;
     if (cached_narrow) { stats.field_mul += (uint64_t)tr.size() * AFX_SECVAR_STORED; return; }   // (2dT of each entry)
-    Launch al;
-    al.kind = L_TABLE_AFFINE;
-    al.njobs = tl.njobs;
-    al.jobs_off = blob_alloc(sizeof(afx_table_job) * tr.size(), 16);
-    memcpy(blob_.data() + al.jobs_off, tr.data(), sizeof(afx_table_job) * tr.size());
+    add_jobs<L_TABLE_AFFINE>(tr);
+    Launch& al = launches.back();
     const uint32_t groups = ctx->walk_rows(count, tr.size(), small());
     add_walk_rows(al, groups > 1 ? (al.njobs + groups - 1) / groups : 0);
-    launches.push_back(al);
     // per entry: the prefix product, 1/Z and the running inverse, x and y, the niels form (4); per row the inversion
     stats.field_mul += (uint64_t)tr.size() * AFX_SECVAR_STORED * 9 + (uint64_t)al.nrows * 11;
     stats.field_sq += (uint64_t)al.nrows * 254;
@@ -907,13 +884,8 @@ void Assembler::msm_list(std::vector<afx_msm_job> jobs, bool no_naf, std::vector
       const std::vector<afx_table_job>& tr = table_rows[odd];
       if (tr.empty()) continue;
       if (odd == 2) { emit_narrow_tables(tr); continue; }
-      Launch tl;
-      tl.kind = L_MSM_TABLES;
-      tl.odd = odd;
-      tl.njobs = (uint32_t)tr.size();
-      tl.jobs_off = blob_alloc(sizeof(afx_table_job) * tr.size(), 16);
-      memcpy(blob_.data() + tl.jobs_off, tr.data(), sizeof(afx_table_job) * tr.size());
-      launches.push_back(tl);
+      add_jobs<L_MSM_TABLES>(tr);
+      launches.back().odd = odd;
     }
     // a launch none of whose jobs encodes inside the kernel (every windowed launch of Issuer::verify: results that are only
     // encoded go through k_compress2x) runs the kernel compiled without the encoder (kernels.hip, k_msm<KIND, ENC>).  Splitting
@@ -966,11 +938,11 @@ void Assembler::from_uniform(const uint8_t* wide, uint8_t* out_enc, int32_t* out
     return;
   }
   const afx_uniform_job j = { wide, out_enc, out_var };
-  add_jobs(L_FROM_UNIFORM, std::vector<afx_uniform_job>(1, j));
+  add_jobs(std::vector<afx_uniform_job>(1, j));
 }
 void Assembler::reduce_wide(const uint8_t* wide, uint8_t* out) {
   const afx_reduce_job j = { wide, out };
-  add_jobs(L_REDUCE_WIDE, std::vector<afx_reduce_job>(1, j));
+  add_jobs(std::vector<afx_reduce_job>(1, j));
 }
 void Assembler::sha512(const afx_sha512_job& job) {
   flush_maps();
@@ -978,7 +950,7 @@ void Assembler::sha512(const afx_sha512_job& job) {
   afx_sha512_job j;
   memset(&j, 0, sizeof j);
   j.src = job.src; j.out = job.out; j.copy = job.copy; j.stride = job.stride; j.offset = job.offset; j.len = job.len;
-  add_jobs(L_SHA512, std::vector<afx_sha512_job>(1, j));
+  add_jobs(std::vector<afx_sha512_job>(1, j));
 }
 void Assembler::encode_to_group(const afx_encode_job& job) {
   flush_maps();
@@ -986,7 +958,7 @@ void Assembler::encode_to_group(const afx_encode_job& job) {
   stats.decodings += 4;   // the mean number of candidates tried
   stats.field_mul += 4 * AFX_DECODE_MUL; stats.field_sq += 4 * AFX_DECODE_SQ;
   stats.chain_mul += 4 * AFX_CHAIN_SQRT_MUL; stats.chain_sq += 4 * AFX_CHAIN_SQRT_SQ;
-  add_jobs(L_ENCODE, std::vector<afx_encode_job>(1, job));
+  add_jobs(std::vector<afx_encode_job>(1, job));
 }
 void Assembler::encode_at(const afx_encode_at_job& job) {
   flush_maps();
@@ -994,14 +966,14 @@ void Assembler::encode_at(const afx_encode_at_job& job) {
   stats.decodings += 1;
   stats.field_mul += AFX_DECODE_MUL; stats.field_sq += AFX_DECODE_SQ;
   stats.chain_mul += AFX_CHAIN_SQRT_MUL; stats.chain_sq += AFX_CHAIN_SQRT_SQ;
-  add_jobs(L_ENCODE_AT, std::vector<afx_encode_at_job>(1, job));
+  add_jobs(std::vector<afx_encode_at_job>(1, job));
 }
 // rows of `count` dwords each: the opening launch's kernel (k_fill_u32) covers that many per grid row
 void Assembler::wipe(void* p, size_t bytes_per_item) {
   flush_maps();
   std::vector<afx_fill_job> jobs;
   for (size_t k = 0; k < bytes_per_item / 4; k++) { const afx_fill_job f = { (uint32_t*)p + k * (size_t)count, 0u, count }; jobs.push_back(f); }
-  add_jobs(L_FILL_BAD, jobs);
+  add_jobs(jobs);
 }
 void Assembler::copy(uint8_t* dst, const uint8_t* src, size_t bytes) {
   Launch l; l.kind = L_COPY; l.in = src; l.out = dst; l.bytes = bytes;
@@ -1012,13 +984,13 @@ void Assembler::mask(const std::vector<uint8_t*>& rows) {
   flush_encodings();   // (the rows' last writers may be encodings a small pass still has queued)
   std::vector<afx_mask_job> jobs;
   for (uint8_t* r : rows) if (r) { const afx_mask_job j = { r }; jobs.push_back(j); }
-  add_jobs(L_MASK, jobs);
+  add_jobs(jobs);
 }
 void Assembler::finish(uint8_t* status_dev, uint8_t fail_code) {
   flush_maps();
   flush_encodings();   // (results no transcript reads; their rejections are flags k_finish folds into the status)
   const afx_finish_job j = { bad_, status_dev, count, fail_code };
-  add_jobs(L_FINISH, std::vector<afx_finish_job>(1, j));
+  add_jobs(std::vector<afx_finish_job>(1, j));
 }
 int Assembler::finish_plan(Plan& out, uint8_t* in_base, size_t in_bytes, uint8_t* out_base, size_t out_bytes) {
   if (!plan_error.empty()) { set_error(plan_error); return AFX_E_BAD_ARGS; }
@@ -1058,50 +1030,9 @@ int Assembler::finish_plan(Plan& out, uint8_t* in_base, size_t in_bytes, uint8_t
 // ------------------------------------------------------------------------------------------------
 Plan::~Plan() { secure_zero(blob.data(), blob.size()); }
 
-namespace {
-// a pointer moves with the range it points into (end inclusive: one-past-the-end pointers of empty rows move along)
-struct Mover {
-  struct R { uintptr_t lo, hi; intptr_t delta; } r[4];
-  template <class T>
-  void fix(T*& p) const {
-    const uintptr_t v = (uintptr_t)p;
-    if (!v) return;
-    for (const R& x : r)
-      if (x.hi > x.lo && v >= x.lo && v <= x.hi) { p = (T*)(v + x.delta); return; }
-  }
-  template <class T>
-  void fix(const T*& p) const { T* q = const_cast<T*>(p); fix(q); p = q; }
-};
-size_t job_size(LaunchKind k) {
-  switch (k) {
-    case L_FILL_BAD: return sizeof(afx_fill_job);
-    case L_DECODE: return sizeof(afx_decode_job);
-    case L_SCCHECK: return sizeof(afx_sccheck_job);
-    case L_POINTOP: return sizeof(afx_pointop_job);
-    case L_SCALAROP: return sizeof(afx_scalarop_job);
-    case L_MSM_WINDOW: case L_MSM_FIXED: case L_MSM_NAF: return sizeof(afx_msm_djob);
-    case L_HASH: return sizeof(afx_hash_program);
-    case L_FROM_UNIFORM: return sizeof(afx_uniform_job);
-    case L_REDUCE_WIDE: return sizeof(afx_reduce_job);
-    case L_FINISH: return sizeof(afx_finish_job);
-    case L_MSM_TABLES: return sizeof(afx_table_job);
-    case L_COMPRESS: return sizeof(afx_compress_job);
-    case L_POINTSUM: return sizeof(afx_pointsum_job);
-    case L_NEGENC: return sizeof(afx_negenc_job);
-    case L_TABLE_AFFINE: return sizeof(afx_table_job);
-    case L_POWERS: return sizeof(afx_powers_job);
-    case L_COEF: return sizeof(afx_coef_job);
-    case L_SHA512: return sizeof(afx_sha512_job);
-    case L_ENCODE: return sizeof(afx_encode_job);
-    case L_MASK: return sizeof(afx_mask_job);
-    case L_ENCODE_AT: return sizeof(afx_encode_at_job);
-    default: return 0;
-  }
-}
-}  // namespace
-
-// Every pointer field of every plan structure, by type.  Side tables that hold pointers themselves (a job's terms, a sum's parts,
-// a transcript's field and output tables) are listed by the Assembler as it writes them (put_ptrs, term_tables_).
+// Every pointer field of every plan structure: the jobs' by their kind's entry in launch_kinds.hpp, the rest here.  Side tables that hold
+// pointers themselves (a job's terms, a sum's parts, a transcript's field and output tables) are listed by the Assembler as it
+// writes them (put_ptrs, term_tables_).
 void Plan::relocate(uint8_t* nblob, uint8_t* nws, uint8_t* nin, uint8_t* nout) {
   if (nblob == blob_base && nws == ws_base && (nin == in_base || !in_bytes) && (nout == out_base || !out_bytes)) return;
   Mover m;
@@ -1122,50 +1053,9 @@ void Plan::relocate(uint8_t* nblob, uint8_t* nws, uint8_t* nin, uint8_t* nout) {
   afx_pass* P = (afx_pass*)(blob.data() + pass_off);
   m.fix(P->bad); m.fix(P->table_ws); m.fix(P->digit_ws);
   for (Launch& l : launches) {
-    uint8_t* J = blob.data() + l.jobs_off;
-    switch (l.kind) {
-      case L_FILL_BAD: for (uint32_t i = 0; i < l.njobs; i++) m.fix(((afx_fill_job*)J)[i].p); break;
-      case L_DECODE: for (uint32_t i = 0; i < l.njobs; i++) { afx_decode_job& j = ((afx_decode_job*)J)[i]; m.fix(j.enc); m.fix(j.out); } break;
-      case L_SCCHECK: for (uint32_t i = 0; i < l.njobs; i++) m.fix(((afx_sccheck_job*)J)[i].sc); break;
-      case L_POINTOP:
-        for (uint32_t i = 0; i < l.njobs; i++) { afx_pointop_job& j = ((afx_pointop_job*)J)[i]; m.fix(j.a); m.fix(j.b); m.fix(j.b_const); m.fix(j.out); m.fix(j.out_enc); }
-        break;
-      case L_SCALAROP: for (uint32_t i = 0; i < l.njobs; i++) { afx_scalarop_job& j = ((afx_scalarop_job*)J)[i]; m.fix(j.a); m.fix(j.b); m.fix(j.c); m.fix(j.out); } break;
-      case L_MSM_WINDOW: case L_MSM_FIXED: case L_MSM_NAF:
-        for (uint32_t i = 0; i < l.njobs; i++) {
-          afx_msm_djob& j = ((afx_msm_djob*)J)[i];
-          m.fix(j.naf_sched); m.fix(j.addend); m.fix(j.out_enc); m.fix(j.out_var); m.fix(j.half_var);
-        }
-        break;
-      case L_MSM_TABLES: case L_TABLE_AFFINE: for (uint32_t i = 0; i < l.njobs; i++) m.fix(((afx_table_job*)J)[i].var); break;
-      case L_COMPRESS: for (uint32_t i = 0; i < l.njobs; i++) { afx_compress_job& j = ((afx_compress_job*)J)[i]; m.fix(j.var); m.fix(j.out_enc); } break;
-      case L_NEGENC: for (uint32_t i = 0; i < l.njobs; i++) { afx_negenc_job& j = ((afx_negenc_job*)J)[i]; m.fix(j.enc); m.fix(j.var); m.fix(j.out_enc); } break;
-      case L_POINTSUM:
-        for (uint32_t i = 0; i < l.njobs; i++) {
-          afx_pointsum_job& j = ((afx_pointsum_job*)J)[i];
-          m.fix(j.parts); m.fix(j.addend); m.fix(j.out_var); m.fix(j.half_var); m.fix(j.out_enc);
-        }
-        break;
-      case L_HASH:
-        for (uint32_t i = 0; i < l.njobs; i++) {
-          afx_hash_program& j = ((afx_hash_program*)J)[i];
-          m.fix(j.init_state); m.fix(j.load_state); m.fix(j.save_state); m.fix(j.records); m.fix(j.fields); m.fix(j.outs); m.fix(j.challenge); m.fix(j.trace);
-        }
-        break;
-      case L_FROM_UNIFORM: for (uint32_t i = 0; i < l.njobs; i++) { afx_uniform_job& j = ((afx_uniform_job*)J)[i]; m.fix(j.wide); m.fix(j.out_enc); m.fix(j.out_var); } break;
-      case L_REDUCE_WIDE: for (uint32_t i = 0; i < l.njobs; i++) { afx_reduce_job& j = ((afx_reduce_job*)J)[i]; m.fix(j.wide); m.fix(j.out); } break;
-      case L_FINISH: for (uint32_t i = 0; i < l.njobs; i++) { afx_finish_job& j = ((afx_finish_job*)J)[i]; m.fix(j.bad); m.fix(j.status); } break;
-      case L_POWERS:
-        for (uint32_t i = 0; i < l.njobs; i++) { afx_powers_job& j = ((afx_powers_job*)J)[i]; m.fix(j.src); for (uint32_t k = 0; k < AFX_POWERS_MAX; k++) m.fix(j.out[k]); }
-        break;
-      case L_COEF: for (uint32_t i = 0; i < l.njobs; i++) { afx_coef_job& j = ((afx_coef_job*)J)[i]; m.fix(j.weights); m.fix(j.triples); m.fix(j.operands); m.fix(j.out); } break;
-      case L_SHA512: for (uint32_t i = 0; i < l.njobs; i++) { afx_sha512_job& j = ((afx_sha512_job*)J)[i]; m.fix(j.src); m.fix(j.out); m.fix(j.copy); } break;
-      case L_ENCODE: for (uint32_t i = 0; i < l.njobs; i++) { afx_encode_job& j = ((afx_encode_job*)J)[i]; m.fix(j.msgs); m.fix(j.M1); m.fix(j.counters); m.fix(j.zero_a); m.fix(j.zero_b); } break;
-      case L_MASK: for (uint32_t i = 0; i < l.njobs; i++) m.fix(((afx_mask_job*)J)[i].p); break;
-      case L_ENCODE_AT: for (uint32_t i = 0; i < l.njobs; i++) { afx_encode_at_job& j = ((afx_encode_at_job*)J)[i]; m.fix(j.msgs); m.fix(j.counters_in); m.fix(j.M1); m.fix(j.zero_a); m.fix(j.zero_b); } break;
-      case L_COPY: m.fix(l.in); m.fix(l.out); break;
-      case L_KINDS: break;
-    }
+    const KindInfo& k = kind_info(l.kind);
+    if (k.fix) k.fix(m, blob.data() + l.jobs_off, l.njobs);
+    m.fix(l.in); m.fix(l.out);   // (L_COPY)
     if (l.nrows) {
       afx_walk_row* rows = (afx_walk_row*)(blob.data() + l.rows_off);
       for (uint32_t i = 0; i < l.nrows; i++) m.fix(rows[i].prefix_ws);
@@ -1204,16 +1094,17 @@ bool Plan::same_as(const Plan& o, std::string* why) const {
           return dev && v >= b && i >= v - b && i < v - b + bytes;
         };
         for (const Launch& l : launches) {
-          const size_t js = job_size(l.kind);
+          const size_t js = kind_info(l.kind).job_size;
+          const std::string name = kind_info(l.kind).name;
           if (js && i >= l.jobs_off && i < l.jobs_off + js * l.njobs)
-            *why += ": launch kind " + std::to_string((int)l.kind) + ", job " + std::to_string((i - l.jobs_off) / js) + ", byte " + std::to_string((i - l.jobs_off) % js) + " of its struct";
-          if (l.nrows && i >= l.rows_off && i < l.rows_off + sizeof(afx_walk_row) * l.nrows) *why += ": walk rows of launch kind " + std::to_string((int)l.kind);
-          regions.push_back({ l.jobs_off, "jobs of launch kind " + std::to_string((int)l.kind) + " x" + std::to_string(l.njobs) });
+            *why += ": " + name + ", job " + std::to_string((i - l.jobs_off) / js) + ", byte " + std::to_string((i - l.jobs_off) % js) + " of its struct";
+          if (l.nrows && i >= l.rows_off && i < l.rows_off + sizeof(afx_walk_row) * l.nrows) *why += ": walk rows of " + name;
+          regions.push_back({ l.jobs_off, "jobs of " + name + " x" + std::to_string(l.njobs) });
           const uint8_t* J = blob.data() + l.jobs_off;
           for (uint32_t k = 0; k < l.njobs; k++) {
             if (l.kind == L_MSM_WINDOW || l.kind == L_MSM_FIXED || l.kind == L_MSM_NAF) {
               const afx_msm_djob& j = ((const afx_msm_djob*)J)[k];
-              if (in(blob_base + (((const uint8_t*)&j - blob.data()) + j.term_off), sizeof(afx_msm_term) * j.n_terms)) *why += ": terms of msm job " + std::to_string(k) + " (launch kind " + std::to_string((int)l.kind) + ")";
+              if (in(blob_base + (((const uint8_t*)&j - blob.data()) + j.term_off), sizeof(afx_msm_term) * j.n_terms)) *why += ": terms of msm job " + std::to_string(k) + " (" + name + ")";
             } else if (l.kind == L_POINTSUM) {
               const afx_pointsum_job& j = ((const afx_pointsum_job*)J)[k];
               if (in(j.parts, 8 * j.n_parts)) *why += ": parts of pointsum job " + std::to_string(k);
@@ -1279,12 +1170,13 @@ int run_plans(afx_ctx* ctx, int lane, Plan* const* plans, size_t n) {
       const Launch& h = plans[lead]->launches[head[lead]];
       Merged mg;
       mg.kind = h.kind; mg.odd = h.odd;
+      const OddRule odd_rule = kind_info(h.kind).odd;
       for (size_t i = lead; i < n; i++) {
         if (head[i] >= plans[i]->launches.size()) continue;
         const Launch& c = plans[i]->launches[head[i]];
-        const bool same = c.kind == h.kind && (h.kind != L_MSM_TABLES || c.odd == h.odd) && (h.kind != L_COPY || i == lead);
+        const bool same = c.kind == h.kind && (odd_rule != ODD_EQUAL || c.odd == h.odd) && (h.kind != L_COPY || i == lead);
         if (!same) continue;
-        if ((h.kind == L_POINTSUM || h.kind == L_DECODE) && c.odd) mg.odd = 1;   // (some job of the merged launch has many parts / is an Elligator map)
+        if (odd_rule == ODD_OR && c.odd) mg.odd = 1;
         mg.parts.push_back({ (uint32_t)i, (uint32_t)head[i] });
         head[i]++;
       }
@@ -1294,7 +1186,7 @@ int run_plans(afx_ctx* ctx, int lane, Plan* const* plans, size_t n) {
     blob_total = (blob_total + 255) & ~size_t(255);
     for (Merged& mg : sched) {
       if (mg.kind == L_COPY) continue;
-      const bool walk = walks(mg.kind);
+      const bool walk = kind_info(mg.kind).walks;
       uint32_t rows = 0;
       for (const Part& p : mg.parts) { const Launch& l = plans[p.plan]->launches[p.launch]; rows += walk ? l.nrows : l.njobs; }
       mg.nrows = rows;
@@ -1320,7 +1212,7 @@ int run_plans(afx_ctx* ctx, int lane, Plan* const* plans, size_t n) {
   if (n > 1) {
     for (const Merged& mg : sched) {
       if (mg.kind == L_COPY) continue;
-      const bool walk = walks(mg.kind);
+      const bool walk = kind_info(mg.kind).walks;
       size_t w = mg.rows_off;
       for (const Part& p : mg.parts) {
         const Plan& pl = *plans[p.plan];
@@ -1335,7 +1227,7 @@ int run_plans(afx_ctx* ctx, int lane, Plan* const* plans, size_t n) {
             w += sizeof row;
           }
         } else {
-          const size_t js = job_size(mg.kind);
+          const size_t js = kind_info(mg.kind).job_size;
           for (uint32_t r = 0; r < l.njobs; r++) {
             const afx_row row = { p.plan, (uint32_t)(boff[p.plan] + l.jobs_off + r * js) };
             memcpy(bhost + w, &row, sizeof row);
@@ -1366,34 +1258,10 @@ int run_plans(afx_ctx* ctx, int lane, Plan* const* plans, size_t n) {
     switch (kind) {
       case L_FILL_BAD: AFX_HIP(afxk_fill_u32(s, (const afx_fill_job*)jobs, nrows, rw, max_count)); break;
       case L_DECODE: AFX_HIP(afxk_decode(s, (const afx_decode_job*)jobs, nrows, rw, passes, max_count, odd)); break;
-      case L_SCCHECK: AFX_HIP(afxk_sccheck(s, (const afx_sccheck_job*)jobs, nrows, rw, passes, max_count)); break;
-      case L_POINTOP: AFX_HIP(afxk_pointop(s, (const afx_pointop_job*)jobs, nrows, rw, passes, max_count)); break;
-      case L_SCALAROP: AFX_HIP(afxk_scalarop(s, (const afx_scalarop_job*)jobs, nrows, rw, passes, max_count)); break;
       case L_COMPRESS: AFX_HIP(afxk_compress2x(s, (const afx_compress_job*)jobs, (const afx_walk_row*)rows, nrows, passes, max_count)); break;
       case L_NEGENC: AFX_HIP(afxk_negenc(s, (const afx_negenc_job*)jobs, (const afx_walk_row*)rows, nrows, passes, max_count)); break;
       case L_TABLE_AFFINE: AFX_HIP(afxk_table_affine(s, (const afx_table_job*)jobs, (const afx_walk_row*)rows, nrows, passes, max_count)); break;
       case L_POINTSUM: AFX_HIP(afxk_pointsum(s, (const afx_pointsum_job*)jobs, nrows, rw, passes, max_count, odd, ctx->variants)); break;
-      case L_POWERS: AFX_HIP(afxk_powers(s, (const afx_powers_job*)jobs, nrows, rw, passes, max_count)); break;
-      case L_COEF:
-        if (!afxk_coef) { set_error("batchable verification: no k_coef launcher in this build"); return AFX_E_NO_DEVICE; }
-        AFX_HIP(afxk_coef(s, (const afx_coef_job*)jobs, nrows, rw, passes, max_count));
-        break;
-      case L_SHA512:
-        if (!afxk_sha512_jobs) { set_error("no k_sha512 launcher in this build"); return AFX_E_NO_DEVICE; }
-        AFX_HIP(afxk_sha512_jobs(s, (const afx_sha512_job*)jobs, nrows, rw, passes, max_count));
-        break;
-      case L_ENCODE:
-        if (!afxk_encode_to_group) { set_error("no k_encode_to_group launcher in this build"); return AFX_E_NO_DEVICE; }
-        AFX_HIP(afxk_encode_to_group(s, (const afx_encode_job*)jobs, nrows, rw, passes, max_count));
-        break;
-      case L_MASK:
-        if (!afxk_mask_rows) { set_error("no k_mask_rows launcher in this build"); return AFX_E_NO_DEVICE; }
-        AFX_HIP(afxk_mask_rows(s, (const afx_mask_job*)jobs, nrows, rw, passes, max_count));
-        break;
-      case L_ENCODE_AT:
-        if (!afxk_encode_at) { set_error("no k_encode_at launcher in this build"); return AFX_E_NO_DEVICE; }
-        AFX_HIP(afxk_encode_at(s, (const afx_encode_at_job*)jobs, nrows, rw, passes, max_count));
-        break;
       case L_MSM_TABLES: AFX_HIP(afxk_msm_tables(s, odd, (const afx_table_job*)jobs, nrows, rw, passes, max_count)); break;
       case L_MSM_FIXED: case L_MSM_WINDOW: case L_MSM_NAF: {
         // pipelined lanes: the heavy kernel of one lane never runs beside the other lane's (only the light kernels
@@ -1412,11 +1280,14 @@ int run_plans(afx_ctx* ctx, int lane, Plan* const* plans, size_t n) {
         if (coop) AFX_HIP(afxk_hash_coop(s, (const afx_hash_program*)jobs, nrows, rw, passes, max_count, ctx->variants));
         else AFX_HIP(afxk_hash(s, (const afx_hash_program*)jobs, nrows, rw, passes, max_count));
         break;
-      case L_FROM_UNIFORM: AFX_HIP(afxk_from_uniform_jobs(s, (const afx_uniform_job*)jobs, nrows, rw, passes, max_count)); break;
-      case L_REDUCE_WIDE: AFX_HIP(afxk_reduce_wide_jobs(s, (const afx_reduce_job*)jobs, nrows, rw, passes, max_count)); break;
       case L_COPY: AFX_HIP(hipMemcpyAsync(copy->out, copy->in, copy->bytes, hipMemcpyDeviceToDevice, s)); break;
       case L_FINISH: AFX_HIP(afxk_finish(s, (const afx_finish_job*)jobs, nrows, rw, max_count)); break;
-      case L_KINDS: break;
+      default: {   // the common signature: the launcher of the kind's entry (launch_kinds.hpp)
+        const KindInfo& k = kind_info(kind);
+        if (!k.run) { set_error(std::string("internal: no launcher for ") + k.name); return AFX_E_BAD_ARGS; }
+        if (int rc = k.run(k, s, jobs, nrows, rw, passes, max_count)) return rc;
+        break;
+      }
     }
     if (ctx->timing) {
       AFX_HIP(hipEventRecord(tl.stop, s));
@@ -1428,7 +1299,7 @@ int run_plans(afx_ctx* ctx, int lane, Plan* const* plans, size_t n) {
     const Plan& pl = *plans[0];
     const afx_pass* passes = (const afx_pass*)(bdev + boff[0] + pl.pass_off);
     for (const Launch& l : pl.launches) {
-      const bool walk = walks(l.kind);
+      const bool walk = kind_info(l.kind).walks;
       const bool coop = l.kind == L_HASH && pl.small && (uint64_t)pl.count * l.njobs <= AFX_HASH_COOP_GROUPS;
       if ((rc = launch(l.kind, l.odd, l.encodes, l.secret, bdev + boff[0] + l.jobs_off, walk ? l.nrows : l.njobs, walk ? (const void*)(bdev + boff[0] + l.rows_off) : nullptr,
                        passes, (const afx_pass*)(pl.blob.data() + pl.pass_off), pl.count, coop, &l)))

@@ -18,6 +18,7 @@
 #include <vector>
 #include "../../include/aeonflux_gpu.h"
 #include "kernels.h"
+#include "launch_kinds.hpp"
 #include "plan.h"
 #include "strobe_sim.hpp"
 
@@ -263,27 +264,18 @@ struct afx_ctx {
   struct TimedLaunch { int kind; hipEvent_t start, stop; };
   std::vector<TimedLaunch> timed;          // recorded, not yet read back
   std::vector<hipEvent_t> event_pool;      // recycled events
-  double kind_ms[32] = { 0 };               // indexed by afx::LaunchKind and, past L_KINDS, afx::TimingSlot
-  uint64_t kind_launches[32] = { 0 };
+  double kind_ms[afx::T_SLOTS] = { 0 };     // indexed by afx::LaunchKind and, past L_KINDS, afx::TimingSlot
+  uint64_t kind_launches[afx::T_SLOTS] = { 0 };
 };
 
 namespace afx {
 
-// L_MSM_WINDOW keeps the slot the single k_msm kernel had (timing names: statements.cpp KIND_NAMES)
-enum LaunchKind { L_FILL_BAD, L_DECODE, L_SCCHECK, L_POINTOP, L_SCALAROP, L_MSM_WINDOW, L_HASH, L_FROM_UNIFORM, L_REDUCE_WIDE, L_COPY, L_FINISH,
-                  L_MSM_FIXED, L_MSM_NAF, L_MSM_TABLES, L_COMPRESS, L_POINTSUM, L_NEGENC, L_TABLE_AFFINE, L_POWERS, L_COEF, L_SHA512, L_ENCODE, L_MASK, L_ENCODE_AT, L_KINDS };
-// Timing slots past the launch kinds: the two cooperative kernels an L_HASH launch may take instead of k_hash (kernels.hip
-// afxk_hash_coop), counted apart so that a test can say which kernel it ran.  "k_hash" (afx_ctx_get_timing) stays the three together.
-enum TimingSlot { T_HASH_COOP = L_KINDS, T_HASH_COOP64, T_SLOTS };
-static_assert(T_SLOTS <= sizeof(afx_ctx::kind_ms) / sizeof(double), "a timing slot per launch kind and cooperative hash kernel");
-// the kernels whose grid rows WALK a range of the launch's jobs (afx_walk_row) instead of taking one job each (afx_row)
-inline bool walks(LaunchKind k) { return k == L_COMPRESS || k == L_NEGENC || k == L_TABLE_AFFINE; }
-
+// One launch of a plan; everything the host knows about its kind is the kind's entry in launch_kinds.hpp (KINDS)
 struct Launch {
   LaunchKind kind;
   size_t jobs_off = 0;      // offset of the job array in the plan's blob
   uint32_t njobs = 0;
-  size_t rows_off = 0;      // L_COMPRESS, L_NEGENC, L_TABLE_AFFINE (walks()): the afx_walk_row array (grid rows; each walks a range of the jobs)
+  size_t rows_off = 0;      // walking kinds (KindInfo::walks): the afx_walk_row array (grid rows; each walks a range of the jobs)
   uint32_t nrows = 0;
   // L_COPY: direct arguments (device-to-device)
   const uint8_t* in = nullptr;
@@ -300,7 +292,7 @@ struct Launch {
 // pointer inside - in the job arrays, in their side tables, in the pass - points into one of four ranges: the plan's own blob,
 // its workspace, and the staged inputs / outputs of the host-pointer call it serves (anything else is context-resident: generator
 // tables, the key, or the caller's own device arrays).  The plan is assembled against PROVISIONAL bases (non-canonical addresses
-// that are never dereferenced) and moved to real ones by relocate(), which knows every pointer field by type (engine.cpp).  That
+// that are never dereferenced) and moved to real ones by relocate(), which knows every pointer field by type (launch_kinds.hpp).  That
 // is what lets a plan be (1) assembled once and reused by later calls of the same statement, shape and size - the host side of a
 // small call was 0.3 ms of its 1.2 ms - and (2) placed next to the plans of OTHER small calls in one blob, workspace and set of
 // kernel launches (run_plans): presentations of 64 shapes in one Issuer::verify stream cost a dozen launches, not 64 dozens.
@@ -418,8 +410,14 @@ class Assembler {
   std::map<const int32_t*, uint32_t> kept_tables_;                   // narrow table slots that stay for the whole pass (segmenting passes: all of them)
   bool segmenting_ = false;                                          // this pass keeps its narrow tables (set by the first segmented stage)
   void compress(const std::vector<afx_compress_job>& cjobs, uint32_t groups);
+  // one launch over `jobs`; the job's type names the kind, except for the structs that serve several kinds (launch_kinds.hpp)
+  template <LaunchKind K, class T>
+  void add_jobs(const std::vector<T>& jobs);
   template <class T>
-  void add_jobs(LaunchKind k, const std::vector<T>& jobs);
+  void add_jobs(const std::vector<T>& jobs) {
+    static_assert(kind_of_job<T>() != L_KINDS, "this job struct serves no launch kind, or several: add_jobs<kind>(jobs)");
+    add_jobs<kind_of_job<T>()>(jobs);
+  }
   void flush_encodings();
   void flush_maps();
   std::vector<afx_decode_job> pending_maps_;         // Elligator maps queued by from_uniform (small passes): they ride in the next decode launch

@@ -44,7 +44,7 @@ hipError_t afxk_hash_coop(hipStream_t s, const afx_hash_program* progs, uint32_t
 hipError_t afxk_finish(hipStream_t s, const afx_finish_job* jobs, uint32_t njobs, const afx_row* rows, uint32_t max_count);
 hipError_t afxk_fill_u32(hipStream_t s, const afx_fill_job* jobs, uint32_t njobs, const afx_row* rows, uint32_t max_n);
 // output masking (plan.h afx_mask_job): the cells of failed items in the listed rows become zeros.  The host sources refer to it through a
-// weak declaration (engine.cpp), like afxk_coef.
+// weak declaration (launch_kinds.hpp), like afxk_coef.
 hipError_t afxk_mask_rows(hipStream_t s, const afx_mask_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count);
 hipError_t afxk_from_uniform_jobs(hipStream_t s, const afx_uniform_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count);
 hipError_t afxk_reduce_wide_jobs(hipStream_t s, const afx_reduce_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count);

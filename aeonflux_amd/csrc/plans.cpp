@@ -240,10 +240,6 @@ static int ensure_pinned(void*& buf, size_t& cap, size_t bytes, size_t granule) 
   return AFX_OK;
 }
 
-// (a weak reference: the host simulation builds of the engine link the launchers they need from tests/hostsim, and their calls never
-// draw unless one of them brings this one - tests/hostsim/fake_draw.cpp)
-hipError_t afxk_draw(hipStream_t s, const afx_draw_job* jobs, uint32_t njobs, uint32_t max_count) __attribute__((weak));
-
 // k_draw over `jobs`, then k_fill_u32 zeroes the staged seeds that `wipes` name - also when the draws could not be launched.  The rows
 // go to the lane's draw_jobs buffer from `img`, which the caller keeps until the lane has been waited for.
 static int run_draws(afx_ctx* c, int lane, const std::vector<afx_draw_job>& jobs, const std::vector<afx_fill_job>& wipes, std::vector<uint8_t>& img) {

@@ -36,12 +36,6 @@ extern "C" const char* afx_last_error(void) { return afx::last_error(); }
 extern "C" uint32_t afx_ctx_n_attributes(const afx_ctx* ctx) { return ctx ? ctx->n : 0; }
 extern "C" void* afx_ctx_stream(const afx_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
-// indexed by afx::LaunchKind, then afx::TimingSlot.  "k_msm" (afx_ctx_get_timing) = the three chain kernels + the table kernel together;
-// "k_hash" = the one-lane kernel + the two cooperative ones together (the slot L_HASH itself holds the one-lane kernel alone)
-static const char* const KIND_NAMES[] = { "k_fill_u32", "k_decode", "k_sccheck", "k_pointop", "k_scalarop", "k_msm_window", "k_hash",
-                                          "k_from_uniform", "k_reduce_wide", "copy", "k_finish", "k_msm_fixed", "k_msm_naf", "k_msm_tables", "k_compress2x", "k_pointsum", "k_negenc", "k_table_affine", "k_powers", "k_coef", "k_sha512", "k_encode_to_group", "k_mask_rows", "k_encode_at",
-                                          "k_hash_coop", "k_hash_coop64" };
-static_assert(sizeof KIND_NAMES / sizeof KIND_NAMES[0] == afx::T_SLOTS, "one name per launch kind and timing slot");
 static int drain_timing(afx_ctx* c) {
   for (auto& L : c->lane)
     if (L.stream) AFX_HIP(hipStreamSynchronize(L.stream));
@@ -241,6 +235,8 @@ extern "C" int afx_ctx_get_timing(afx_ctx* c, const char* kernel, double* total_
   AFX_HIP(hipSetDevice(c->device));
   int rc = drain_timing(c);
   if (rc) return rc;
+  // "k_msm" = the three chain kernels + the table kernel together; "k_hash" = the one-lane kernel + the two cooperative ones together
+  // (the slot L_HASH itself holds the one-lane kernel alone); every other name is a slot's own (afx::timing_name)
   if (strcmp(kernel, "k_msm") == 0) {
     *total_ms = 0; *launches = 0;
     for (int k : { (int)L_MSM_WINDOW, (int)L_MSM_FIXED, (int)L_MSM_NAF, (int)L_MSM_TABLES }) { *total_ms += c->kind_ms[k]; *launches += c->kind_launches[k]; }
@@ -251,8 +247,8 @@ extern "C" int afx_ctx_get_timing(afx_ctx* c, const char* kernel, double* total_
     for (int k : { (int)L_HASH, (int)T_HASH_COOP, (int)T_HASH_COOP64 }) { *total_ms += c->kind_ms[k]; *launches += c->kind_launches[k]; }
     return AFX_OK;
   }
-  for (size_t k = 0; k < sizeof KIND_NAMES / sizeof KIND_NAMES[0]; k++)
-    if (strcmp(kernel, KIND_NAMES[k]) == 0) { *total_ms = c->kind_ms[k]; *launches = c->kind_launches[k]; return AFX_OK; }
+  for (int k = 0; k < (int)afx::T_SLOTS; k++)
+    if (strcmp(kernel, afx::timing_name(k)) == 0) { *total_ms = c->kind_ms[k]; *launches = c->kind_launches[k]; return AFX_OK; }
   set_error("unknown kernel name");
   return AFX_E_BAD_ARGS;
 } catch (...) { return afx::exception_rc(); }
@@ -734,9 +730,6 @@ extern "C" int afx_verify_presentations_dev(afx_ctx* ctx, const afx_shape* shape
 // ------------------------------------------------------------------------------------------------
 // batchable presentation proofs: the verifier (include/aeonflux_gpu.h)
 // ------------------------------------------------------------------------------------------------
-// (weak, like afxk_coef in engine.cpp: a host simulation that never verifies a batchable proof links without it)
-hipError_t afxk_batch_weights(hipStream_t s, const uint8_t* seed, uint64_t index0, uint32_t label, uint32_t n_weights, uint32_t count, uint8_t* weights) __attribute__((weak));
-
 extern "C" uint32_t afx_batchable_main_commitments(const afx_ctx* ctx, const afx_shape* shape) {
   if (!ctx || !shape) return 0;
   uint32_t keep[AFX_MAX_ATTRIBUTES], pos[AFX_MAX_ATTRIBUTES], k = 0;

@@ -10,14 +10,7 @@
 // rows wherever afx_ctx_set_chunk_items falls and a message's chunks straddle passes.  Everything runs in order on lane 0's stream.
 #include "statements.hpp"
 
-// Weak references, as in statements_setup.cpp: a build without kernels.hip's launchers answers AFX_E_NO_DEVICE.
-hipError_t afxk_sha512_jobs(hipStream_t s, const afx_sha512_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
-hipError_t afxk_encode_to_group(hipStream_t s, const afx_encode_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
-hipError_t afxk_encode_at(hipStream_t s, const afx_encode_at_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
-hipError_t afxk_mask_rows(hipStream_t s, const afx_mask_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
-hipError_t afxk_msg_gather(hipStream_t s, const afx_gather_job* job) __attribute__((weak));
-hipError_t afxk_msg_expand(hipStream_t s, const afx_expand_job* job) __attribute__((weak));
-hipError_t afxk_msg_status(hipStream_t s, const afx_msgstat_job* job) __attribute__((weak));
+// (weak references, launch_kinds.hpp: a build without kernels.hip's launchers answers AFX_E_NO_DEVICE)
 static int need_message_kernels() {
   if (afxk_sha512_jobs && afxk_encode_to_group && afxk_encode_at && afxk_mask_rows && afxk_msg_gather && afxk_msg_expand && afxk_msg_status) return AFX_OK;
   set_error("no whole-message kernels (k_msg_gather, k_msg_expand, k_msg_status, k_encode_at) in this build");

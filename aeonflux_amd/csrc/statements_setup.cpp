@@ -10,11 +10,8 @@
 #include "sha512_host.hpp"   // (only the bodies kept for builds without the hash kernels read it: see have_hash_kernels)
 #include "statements.hpp"
 
-// Weak references, like afxk_coef in engine.cpp: the host simulation of tests/test_hostsim.py links the engine against stand-in
-// launchers that know nothing of these three, and its calls of afx_keypairs_derive, afx_encrypt and afx_decrypt must still succeed.
-hipError_t afxk_sha512_jobs(hipStream_t s, const afx_sha512_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
-hipError_t afxk_encode_to_group(hipStream_t s, const afx_encode_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
-hipError_t afxk_sha512(hipStream_t s, const uint8_t* src, uint32_t stride, uint32_t offset, uint32_t len, uint8_t* out, uint32_t count) __attribute__((weak));
+// The host simulation of tests/test_hostsim.py links the engine against stand-in launchers that know nothing of the three hash
+// launchers (weak references, launch_kinds.hpp), and its calls of afx_keypairs_derive, afx_encrypt and afx_decrypt must still succeed.
 // false only in a build without kernels.hip's launchers (a host simulation): the three host-pointer calls that hash then take the
 // bodies below that hash on the host (*_without_hash_kernels), which exist for such builds alone - the library never does
 static bool have_hash_kernels() { return afxk_sha512_jobs && afxk_encode_to_group && afxk_sha512; }
