@@ -156,8 +156,10 @@ AFX_DEV ge_p1p1 ge_madd(const ge_p3& p, const ge_niels& q, bool neg) {
   r.T = fe_add(D, Cn);
   return r;
 }
-AFX_DEV ge_p3 ge_add(const ge_p3& p, const ge_p3& q) { return ge_p1p1_to_p3(ge_add_cached(p, ge_p3_to_cached(q), false)); }
-AFX_DEV ge_p3 ge_sub(const ge_p3& p, const ge_p3& q) { return ge_p1p1_to_p3(ge_add_cached(p, ge_p3_to_cached(q), true)); }
+// extended plus (neg: minus) extended, everything centred on the way out; q centred (ge_p3_to_cached)
+AFX_DEV ge_p3 ge_addsub(const ge_p3& p, const ge_p3& q, bool neg) { return ge_p1p1_to_p3(ge_add_cached(p, ge_p3_to_cached(q), neg)); }
+AFX_DEV ge_p3 ge_add(const ge_p3& p, const ge_p3& q) { return ge_addsub(p, q, false); }
+AFX_DEV ge_p3 ge_sub(const ge_p3& p, const ge_p3& q) { return ge_addsub(p, q, true); }
 AFX_DEV ge_p3 ge_neg(const ge_p3& p) {
   ge_p3 r;
   r.X = fe_neg(p.X); r.Y = p.Y; r.Z = p.Z; r.T = fe_neg(p.T);

@@ -223,17 +223,35 @@ AFX_DEV const T* row_job(const T* __restrict__ jobs, const afx_row* __restrict__
   return jobs + blockIdx.y;
 }
 AFX_DEV uint32_t row_pass_index(const afx_row* __restrict__ rows) { return rows ? rows[blockIdx.y].pass : 0u; }
+// What a kernel asks of its grid row before it starts, in the three ways a block is laid over a pass's items.  The grid is sized for
+// the launch's largest pass, so every way has its test for the end of THIS row's pass.
+// A lane per item: the row's job, its pass's count and flags, the lane's item; a lane past the end retires (`item >= count`).
+template <class T> struct lane_row { T job; uint32_t count; uint32_t* bad; uint32_t item; };
+template <class T>
+AFX_DEV lane_row<T> lane_row_of(const T* __restrict__ jobs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
+  const afx_pass pass = passes[row_pass_index(rows)];   // wave-uniform: scalar loads
+  return { *row_job(jobs, rows), pass.count, pass.bad, blockIdx.x * blockDim.x + threadIdx.x };
+}
+// A lane per item whose live waves stay whole (the chain and table kernels: msm_add_positional_secret's exchange needs every lane
+// of a live wave active): a WAVE past the end of this row's pass retires (a pass of 16 items is one wave of its block's four; no
+// kernel here has a barrier).  Inside the last live wave, lanes past the end shadow the last item (identical values, identical stores).
+AFX_DEV bool wave_past_end(uint32_t count) {
+  return blockIdx.x * blockDim.x + ((uint32_t)__builtin_amdgcn_readfirstlane((int)threadIdx.x) & ~63u) >= count;   // (first lane's id: the branch is scalar)
+}
+AFX_DEV uint32_t shadowing_item(uint32_t count) { return min(blockIdx.x * blockDim.x + threadIdx.x, count - 1); }
+// Four waves = four roles over the same 64 items (k_msm_quad below; msm_quad_body states the same three values for its lambdas): a
+// block past the end retires first (`blockIdx.x * 64u >= count`, block-uniform: the barriers stay whole); then lane = the item's
+// place in the block, role = the wave (first lane's id: scalar), and lanes past the end shadow the last item.
+struct quad_seat { uint32_t lane, role, item; };
+AFX_DEV quad_seat quad_seat_of(uint32_t count) {
+  const uint32_t lane = threadIdx.x & 63u;
+  return { lane, (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), min(blockIdx.x * 64u + lane, count - 1) };
+}
 
 // ---------------------------------------------------------------------------------------------
 // decode / scalar checks / small point and scalar ops
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(AFX_BLOCK, 2) k_decode(const afx_decode_job* __restrict__ jobs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
-  const afx_decode_job job = *row_job(jobs, rows);
-  const afx_pass pass = passes[row_pass_index(rows)];   // wave-uniform: scalar loads
-  const uint32_t count = pass.count;
-  uint32_t* __restrict__ bad = pass.bad;
-  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
-  if (item >= count) return;
+AFX_DEV void decode_item(const afx_decode_job& job, uint32_t* bad, uint32_t count, uint32_t item) {
   uint32_t w[8];
   enc_load(w, job.enc, item);
   ge_p3 P;
@@ -242,56 +260,43 @@ __global__ void __launch_bounds__(AFX_BLOCK, 2) k_decode(const afx_decode_job* _
   if (job.reject_identity && is_identity_encoding(w)) flags |= AFX_BAD_IDENTITY;
   if (flags) atomicOr(&bad[item], flags);
   if (job.out) var_store(job.out, count, item, ok ? P : ge_identity());
+}
+__global__ void __launch_bounds__(AFX_BLOCK, 2) k_decode(const afx_decode_job* __restrict__ jobs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
+  const auto [job, count, bad, item] = lane_row_of(jobs, rows, passes);
+  if (item >= count) return;
+  decode_item(job, bad, count, item);
 }
 
 // the same for a small pass's launch that also holds Elligator jobs (afx_decode_job.elligator): two kinds of square-root chain side by
 // side in one launch, a grid row each, instead of one launch after the other
 __global__ void __launch_bounds__(AFX_BLOCK) k_decode_mixed(const afx_decode_job* __restrict__ jobs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
-  const afx_decode_job job = *row_job(jobs, rows);
-  const afx_pass pass = passes[row_pass_index(rows)];   // wave-uniform: scalar loads
-  const uint32_t count = pass.count;
-  uint32_t* __restrict__ bad = pass.bad;
-  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
+  const auto [job, count, bad, item] = lane_row_of(jobs, rows, passes);
   if (item >= count) return;
-  uint32_t w[8];
   if (job.elligator) {   // (uniform)
+    uint32_t w[8];
     enc_load(w, job.enc, 2 * item + (job.elligator - 1));
     var_store(job.out, count, item, ristretto_elligator(fe_frombytes(w)));
     return;
   }
-  enc_load(w, job.enc, item);
-  ge_p3 P;
-  const bool ok = ristretto_decode(P, w);
-  uint32_t flags = ok ? 0u : AFX_BAD_DECODE;
-  if (job.reject_identity && is_identity_encoding(w)) flags |= AFX_BAD_IDENTITY;
-  if (flags) atomicOr(&bad[item], flags);
-  if (job.out) var_store(job.out, count, item, ok ? P : ge_identity());
+  decode_item(job, bad, count, item);
 }
 
 __global__ void __launch_bounds__(AFX_BLOCK) k_sccheck(const afx_sccheck_job* __restrict__ jobs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
-  const afx_sccheck_job job = *row_job(jobs, rows);
-  const afx_pass pass = passes[row_pass_index(rows)];   // wave-uniform: scalar loads
-  const uint32_t count = pass.count;
-  uint32_t* __restrict__ bad = pass.bad;
-  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
+  const auto [job, count, bad, item] = lane_row_of(jobs, rows, passes);
   if (item >= count) return;
   const sc s = sc_load_item(job.sc, 32, item);
   if (!sc_is_canonical(s)) atomicOr(&bad[item], AFX_BAD_SCALAR);
 }
 
 __global__ void __launch_bounds__(AFX_BLOCK, 2) k_pointop(const afx_pointop_job* __restrict__ jobs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
-  const afx_pointop_job job = *row_job(jobs, rows);
-  const afx_pass pass = passes[row_pass_index(rows)];   // wave-uniform: scalar loads
-  const uint32_t count = pass.count;
-  uint32_t* __restrict__ bad = pass.bad;
-  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
+  const auto [job, count, bad, item] = lane_row_of(jobs, rows, passes);
   if (item >= count) return;
   ge_p3 A = var_load(job.a, count, item);
   if (job.sa < 0) A = ge_neg(A);
   ge_p3 R = A;
   if (job.sb != 0) {
     const ge_p3 B = job.b ? var_load(job.b, count, item) : p3_load_uniform(job.b_const);
-    R = ge_p1p1_to_p3(ge_add_cached(A, ge_p3_to_cached(B), job.sb < 0));
+    R = ge_addsub(A, B, job.sb < 0);
   } else {
     R = ge_carry(R);
   }
@@ -306,10 +311,7 @@ __global__ void __launch_bounds__(AFX_BLOCK, 2) k_pointop(const afx_pointop_job*
 }
 
 __global__ void __launch_bounds__(AFX_BLOCK) k_scalarop(const afx_scalarop_job* __restrict__ jobs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
-  const afx_scalarop_job job = *row_job(jobs, rows);
-  const afx_pass pass = passes[row_pass_index(rows)];   // wave-uniform: scalar loads
-  const uint32_t count = pass.count;
-  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
+  const auto [job, count, bad, item] = lane_row_of(jobs, rows, passes);
   if (item >= count) return;
   const sc a = sc_load_item(job.a, job.a_stride, item);
   const sc b = sc_load_item(job.b, job.b_stride, item);
@@ -595,12 +597,13 @@ AFX_DEV ge_p3 msm_fixed_terms(const msm_env& e, const int32_t* __restrict__ pos_
   }
   return acc;
 }
-// addend, extended-coordinate output, compressed output (ENC = false: a launch none of whose jobs encodes here)
-template <bool ENC>
-AFX_DEV void msm_finish(const afx_msm_djob* job, ge_p3 acc, uint32_t* __restrict__ bad, uint32_t count, uint32_t item) {
+// How a sum ends, a chain's (afx_msm_djob) or a k_pointsum's (afx_pointsum_job): addend, extended-coordinate output, compressed
+// output (ENC = false: a launch none of whose jobs encodes here)
+template <bool ENC, class JOB>
+AFX_DEV void sum_finish(const JOB* job, ge_p3 acc, uint32_t* __restrict__ bad, uint32_t count, uint32_t item) {
   if (job->addend) {
     const ge_p3 A = var_load(job->addend, count, item);
-    acc = ge_p1p1_to_p3(ge_add_cached(acc, ge_p3_to_cached(A), job->addend_negate != 0));
+    acc = ge_p1p1_to_p3(ge_add_cached(acc, ge_p3_to_cached(A), job->addend_negate != 0));   // (ge_addsub, spelled out: the sign is read after A's conversion, as the chain kernels were scheduled)
   }
   if (job->out_var) var_store(job->out_var, count, item, acc);
   if (job->half_var) { var_store(job->half_var, count, item, acc); return; }   // encoded by k_compress2x
@@ -622,10 +625,8 @@ k_msm_tables(const afx_table_job* __restrict__ jobs, const afx_row* __restrict__
   const afx_pass pass = passes[row_pass_index(rows)];   // wave-uniform: scalar loads
   const uint32_t count = pass.count;
   int32_t* __restrict__ table_ws = pass.table_ws;
-  // a WAVE past the end of this row's pass retires (the grid is sized for the launch's largest pass, and a pass of 16 items is one wave
-  // of its block's four; no kernel here has a barrier).  Inside the last live wave, lanes past the end shadow the last item.
-  if (blockIdx.x * blockDim.x + ((uint32_t)__builtin_amdgcn_readfirstlane((int)threadIdx.x) & ~63u) >= count) return;   // (first lane's id: the branch is scalar)
-  const uint32_t item = min(blockIdx.x * blockDim.x + threadIdx.x, count - 1);
+  if (wave_past_end(count)) return;
+  const uint32_t item = shadowing_item(count);
   const afx_table_job row = *row_job(jobs, rows);
   int32_t* slot = table_ws + (size_t)row.table_slot * count * AFX_VAR_TABLE_DWORDS;
   const ge_p3 P = var_load(row.var, count, item);
@@ -707,11 +708,8 @@ __device__ __forceinline__ void msm_body(const afx_msm_djob* __restrict__ job, c
   }
   unsigned long long c0 = 0, r0 = 0;
   if (probe) { c0 = clock64(); r0 = wall_clock64(); }
-  // a WAVE past the end of this row's pass retires (the grid is sized for the launch's largest pass, and a pass of 16 items is one wave
-  // of its block's four; no kernel here has a barrier).  Inside the last live wave, lanes past the end shadow the last item.
-  if (blockIdx.x * blockDim.x + ((uint32_t)__builtin_amdgcn_readfirstlane((int)threadIdx.x) & ~63u) >= count) return;   // (first lane's id: the branch is scalar)
-  // lanes past the end of the batch shadow the last item (identical values, identical stores)
-  const uint32_t item = min(blockIdx.x * blockDim.x + threadIdx.x, count - 1);
+  if (wave_past_end(count)) return;
+  const uint32_t item = shadowing_item(count);
   const uint32_t nt = job->n_terms, nv = job->n_var, nu = job->n_uni;
   msm_env env;
   env.job = job; env.term = afx_job_terms(job); env.table_ws = table_ws; env.digit_ws = digit_ws;
@@ -774,7 +772,7 @@ __device__ __forceinline__ void msm_body(const afx_msm_djob* __restrict__ job, c
     // the fixed bases of a job with variable bases: after the chain (any order gives the same sum)
     if (nt != nv) acc = msm_fixed_terms<SEC>(env, pos_tables, sec_tables, acc, nv, nt);
   }
-  msm_finish<ENC>(job, acc, bad, count, item);
+  sum_finish<ENC>(job, acc, bad, count, item);
   if (probe) {
     const unsigned long long dc = (unsigned long long)clock64() - c0, dr = (unsigned long long)wall_clock64() - r0;
     if (threadIdx.x == 0) {
@@ -1102,7 +1100,7 @@ __device__ __forceinline__ void msm_quad_body(const afx_msm_djob* __restrict__ j
       }
     }
   }
-  if (role == 0) msm_finish<false>(job, acc, bad, count, item);
+  if (role == 0) sum_finish<false>(job, acc, bad, count, item);
 }
 template <bool SEC>
 __global__ void __launch_bounds__(256, 2)
@@ -1137,9 +1135,8 @@ k_pointsum_quad(const afx_pointsum_job* __restrict__ jobs, const afx_row* __rest
   const afx_pass pass = passes[row_pass_index(rows)];   // block-uniform: scalar loads
   const uint32_t count = pass.count;
   uint32_t* __restrict__ bad = pass.bad;
-  if (blockIdx.x * 64u >= count) return;   // block-uniform
-  const uint32_t lane = threadIdx.x & 63u, role = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint32_t item = min(blockIdx.x * 64u + lane, count - 1);   // lanes past the end shadow the last item
+  if (blockIdx.x * 64u >= count) return;
+  const auto [lane, role, item] = quad_seat_of(count);
   ge_p3 acc = ge_identity();
   if (role < job.n_parts) {
     acc = var_load(job.parts[role], count, item);
@@ -1149,27 +1146,18 @@ k_pointsum_quad(const afx_pointsum_job* __restrict__ jobs, const afx_row* __rest
     for (uint32_t k = role + 4; k < job.n_parts; k += 4) {
       const ge_p3 cur = nxt;
       if (k + 4 < job.n_parts) nxt = var_load(job.parts[k + 4], count, item);
-      acc = ge_p1p1_to_p3(ge_add_cached(acc, ge_p3_to_cached(cur), false));
+      acc = ge_add(acc, cur);
     }
   }
   // (fewer than 3 parts: the upper roles hold the identity, whose addition changes nothing)
   if (role & 1u) quad_put_point(L, (int)(role >> 1), lane, acc);
   __syncthreads();
-  if (!(role & 1u)) acc = ge_p1p1_to_p3(ge_add_cached(acc, ge_p3_to_cached(quad_get_point(L, (int)(role >> 1), lane)), false));
+  if (!(role & 1u)) acc = ge_add(acc, quad_get_point(L, (int)(role >> 1), lane));
   __syncthreads();
   if (role == 2) quad_put_point(L, 0, lane, acc);
   __syncthreads();
   if (role != 0) return;
-  acc = ge_p1p1_to_p3(ge_add_cached(acc, ge_p3_to_cached(quad_get_point(L, 0, lane)), false));
-  if (job.addend) acc = ge_p1p1_to_p3(ge_add_cached(acc, ge_p3_to_cached(var_load(job.addend, count, item)), job.addend_negate != 0));
-  if (job.out_var) var_store(job.out_var, count, item, acc);
-  if (job.half_var) { var_store(job.half_var, count, item, acc); return; }   // encoded by k_compress2x
-  if (job.out_enc) {
-    uint32_t w[8];
-    ristretto_encode(w, acc);
-    enc_store(job.out_enc, item, w);
-    if (job.reject_identity && is_identity_encoding(w)) atomicOr(&bad[item], AFX_BAD_IDENTITY);
-  }
+  sum_finish<true>(&job, ge_add(acc, quad_get_point(L, 0, lane)), bad, count, item);
 }
 
 // k_pointsum for a job of MANY parts in a pass of few items (a segmenting pass: eight segments per base and a chain per generator
@@ -1187,7 +1175,7 @@ k_pointsum_tree(const afx_pointsum_job* __restrict__ jobs, const afx_row* __rest
   ge_p3 acc = ge_identity();
   if (tid < job.n_parts) acc = var_load(job.parts[tid], count, item);
 #pragma unroll 1
-  for (uint32_t k = tid + 256u; k < job.n_parts; k += 256u) acc = ge_p1p1_to_p3(ge_add_cached(acc, ge_p3_to_cached(var_load(job.parts[k], count, item)), false));
+  for (uint32_t k = tid + 256u; k < job.n_parts; k += 256u) acc = ge_add(acc, var_load(job.parts[k], count, item));
 #pragma unroll 1
   for (uint32_t stride = 128; stride >= 1; stride >>= 1) {
     if (stride >= n) continue;   // (uniform) nothing up there
@@ -1205,20 +1193,11 @@ k_pointsum_tree(const afx_pointsum_job* __restrict__ jobs, const afx_row* __rest
       for (int l = 0; l < AFX_FE_LIMBS; l++) {
         o.X.v[l] = S[l][tid]; o.Y.v[l] = S[AFX_FE_LIMBS + l][tid]; o.Z.v[l] = S[2 * AFX_FE_LIMBS + l][tid]; o.T.v[l] = S[3 * AFX_FE_LIMBS + l][tid];
       }
-      acc = ge_p1p1_to_p3(ge_add_cached(acc, ge_p3_to_cached(o), false));
+      acc = ge_add(acc, o);
     }
     __syncthreads();
   }
-  if (tid != 0) return;
-  if (job.addend) acc = ge_p1p1_to_p3(ge_add_cached(acc, ge_p3_to_cached(var_load(job.addend, count, item)), job.addend_negate != 0));
-  if (job.out_var) var_store(job.out_var, count, item, acc);
-  if (job.half_var) { var_store(job.half_var, count, item, acc); return; }   // encoded by k_compress2x
-  if (job.out_enc) {
-    uint32_t w[8];
-    ristretto_encode(w, acc);
-    enc_store(job.out_enc, item, w);
-    if (job.reject_identity && is_identity_encoding(w)) atomicOr(&bad[item], AFX_BAD_IDENTITY);
-  }
+  if (tid == 0) sum_finish<true>(&job, acc, bad, count, item);
 }
 
 // k_powers: src * 2^step, * 2^(2 step), ... (plan.h afx_powers_job), four waves per item chain like k_msm_quad - these doublings are
@@ -1230,9 +1209,8 @@ k_powers_quad(const afx_powers_job* __restrict__ jobs, const afx_row* __restrict
   const afx_powers_job job = *row_job(jobs, rows);
   const afx_pass pass = passes[row_pass_index(rows)];   // block-uniform: scalar loads
   const uint32_t count = pass.count;
-  if (blockIdx.x * 64u >= count) return;   // block-uniform
-  const uint32_t lane = threadIdx.x & 63u, role = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint32_t item = min(blockIdx.x * 64u + lane, count - 1);   // lanes past the end shadow the last item
+  if (blockIdx.x * 64u >= count) return;
+  const auto [lane, role, item] = quad_seat_of(count);
   ge_p3 acc = var_load(job.src, count, item);
   int buf = 0;
 #pragma unroll 1
@@ -1353,24 +1331,12 @@ k_negenc(const afx_negenc_job* __restrict__ jobs, const afx_walk_row* __restrict
 
 // k_pointsum: out = sum of the partial results of a job that Assembler::msm_split cut into one chain per term (+- addend)
 __global__ void __launch_bounds__(AFX_BLOCK, 2) k_pointsum(const afx_pointsum_job* __restrict__ jobs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
-  const afx_pointsum_job job = *row_job(jobs, rows);
-  const afx_pass pass = passes[row_pass_index(rows)];   // wave-uniform: scalar loads
-  const uint32_t count = pass.count;
-  uint32_t* __restrict__ bad = pass.bad;
-  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
+  const auto [job, count, bad, item] = lane_row_of(jobs, rows, passes);
   if (item >= count) return;
   ge_p3 acc = var_load(job.parts[0], count, item);
 #pragma unroll 1
-  for (uint32_t k = 1; k < job.n_parts; k++) acc = ge_p1p1_to_p3(ge_add_cached(acc, ge_p3_to_cached(var_load(job.parts[k], count, item)), false));
-  if (job.addend) acc = ge_p1p1_to_p3(ge_add_cached(acc, ge_p3_to_cached(var_load(job.addend, count, item)), job.addend_negate != 0));
-  if (job.out_var) var_store(job.out_var, count, item, acc);
-  if (job.half_var) { var_store(job.half_var, count, item, acc); return; }   // encoded by k_compress2x
-  if (job.out_enc) {
-    uint32_t w[8];
-    ristretto_encode(w, acc);
-    enc_store(job.out_enc, item, w);
-    if (job.reject_identity && is_identity_encoding(w)) atomicOr(&bad[item], AFX_BAD_IDENTITY);
-  }
+  for (uint32_t k = 1; k < job.n_parts; k++) acc = ge_add(acc, var_load(job.parts[k], count, item));
+  sum_finish<true>(&job, acc, bad, count, item);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1379,6 +1345,43 @@ __global__ void __launch_bounds__(AFX_BLOCK, 2) k_pointsum(const afx_pointsum_jo
 AFX_DEV uint64_t load_u64(const uint8_t* p) {
   const uint2 v = *reinterpret_cast<const uint2*>(p);
   return (uint64_t)v.x | ((uint64_t)v.y << 32);
+}
+// The steps of a transcript that the three kernels below share; they differ in which lanes hold the state and how it is permuted.
+// fetch: the two 8-byte halves a rate word takes from the item's 32 bytes of its field (plan.h afx_hash_word: q, -1..3); zeros
+// where the word takes none.
+struct hash_halves { uint64_t lo, hi; };
+AFX_DEV hash_halves fetch(const afx_hash_program* prog, const afx_hash_word& hw, uint32_t item) {
+  hash_halves h = { 0ull, 0ull };
+  if (hw.field >= 0) {
+    const uint8_t* f = prog->fields[hw.field] + 32ull * item;
+    h.lo = (hw.q >= 0) ? load_u64(f + 8 * hw.q) : 0ull;
+    h.hi = (hw.q < 3) ? load_u64(f + 8 * (hw.q + 1)) : 0ull;
+  }
+  return h;
+}
+// absorbed: word `st` of the state once a record's rate word has gone in: (st & keep) ^ c ^ (the field's bytes, rotated into place, & fmask)
+AFX_DEV uint64_t absorbed(uint64_t st, const afx_hash_word& hw, const hash_halves& h) {
+  uint64_t v = hw.c;
+  if (hw.field >= 0) {
+    const uint32_t sh = 8u * hw.r;
+    const uint64_t val = sh ? ((h.lo >> sh) | (h.hi << (64u - sh))) : h.lo;
+    v ^= val & hw.fmask;
+  }
+  return (st & hw.keep) ^ v;
+}
+// release_scalar: the 64 squeezed bytes `x` leave as a scalar mod l - compared with the proof's challenge (and traced), or stored
+AFX_DEV void release_scalar(const afx_hash_program* prog, const afx_hash_record* rec, const uint32_t x[16], uint32_t* bad, uint32_t item) {
+  const sc c = sc_reduce512(x);
+  uint32_t w8[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) w8[i] = c.v[i];
+  if (rec->squeeze == AFX_SQ_CHALLENGE_COMPARE) {
+    const sc want = sc_load_item(prog->challenge, 32, item);
+    if (!sc_eq(c, want)) atomicOr(&bad[item], AFX_BAD_CHALLENGE);
+    if (prog->trace) enc_store(prog->trace, item, w8);
+  } else {
+    enc_store(prog->outs[rec->squeeze_out], item, w8);
+  }
 }
 
 __global__ void __launch_bounds__(AFX_BLOCK) k_hash(const afx_hash_program* __restrict__ progs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
@@ -1403,17 +1406,7 @@ __global__ void __launch_bounds__(AFX_BLOCK) k_hash(const afx_hash_program* __re
 #pragma unroll
     for (int w = 0; w < 21; w++) {
       const afx_hash_word hw = rec->w[w];
-      uint64_t v = hw.c;
-      if (hw.field >= 0) {
-        const uint8_t* f = prog->fields[hw.field] + 32ull * item;
-        const int q = hw.q;
-        const uint64_t lo = (q >= 0) ? load_u64(f + 8 * q) : 0ull;
-        const uint64_t hi = (q < 3) ? load_u64(f + 8 * (q + 1)) : 0ull;
-        const uint32_t sh = 8u * hw.r;
-        const uint64_t val = sh ? ((lo >> sh) | (hi << (64u - sh))) : lo;
-        v ^= val & hw.fmask;
-      }
-      st[w] = (st[w] & hw.keep) ^ v;
+      st[w] = absorbed(st[w], hw, fetch(prog, hw, item));
     }
     keccak_f1600(st);
     if (rec->squeeze == AFX_SQ_WIDE_OUT) {   // uniform
@@ -1424,22 +1417,7 @@ __global__ void __launch_bounds__(AFX_BLOCK) k_hash(const afx_hash_program* __re
       uint32_t x[16];
 #pragma unroll
       for (int i = 0; i < 8; i++) { x[2 * i] = (uint32_t)st[i]; x[2 * i + 1] = (uint32_t)(st[i] >> 32); }
-      const sc c = sc_reduce512(x);
-      if (rec->squeeze == AFX_SQ_CHALLENGE_COMPARE) {
-        const sc want = sc_load_item(prog->challenge, 32, item);
-        if (!sc_eq(c, want)) atomicOr(&bad[item], AFX_BAD_CHALLENGE);
-        if (prog->trace) {
-          uint32_t w8[8];
-#pragma unroll
-          for (int i = 0; i < 8; i++) w8[i] = c.v[i];
-          enc_store(prog->trace, item, w8);
-        }
-      } else {
-        uint32_t w8[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) w8[i] = c.v[i];
-        enc_store(prog->outs[rec->squeeze_out], item, w8);
-      }
+      release_scalar(prog, rec, x, bad, item);
     }
   }
   if (prog->save_state) {
@@ -1500,35 +1478,19 @@ __global__ void __launch_bounds__(AFX_BLOCK) k_hash_coop(const afx_hash_program*
   // permutation's own 24 rounds.  (No record reads what a squeeze of its own program stored: SchnorrBuilder::make_program checks.)
   const uint32_t wl = w < 21u ? w : 0u;
   afx_hash_word hw_n = prog->records[0].w[wl];
-  uint64_t lo_n = 0, hi_n = 0;
-  if (w < 21u && hw_n.field >= 0) {
-    const uint8_t* f = prog->fields[hw_n.field] + 32ull * item;
-    lo_n = (hw_n.q >= 0) ? load_u64(f + 8 * hw_n.q) : 0ull;
-    hi_n = (hw_n.q < 3) ? load_u64(f + 8 * (hw_n.q + 1)) : 0ull;
-  }
+  hash_halves h_n = { 0ull, 0ull };
+  if (w < 21u) h_n = fetch(prog, hw_n, item);
 #pragma unroll 1
   for (uint32_t r = 0; r < nrec; r++) {
     const afx_hash_record* rec = &prog->records[r];
     const afx_hash_word hw = hw_n;
-    const uint64_t lo = lo_n, hi = hi_n;
+    const hash_halves h = h_n;
     if (r + 1 < nrec) {   // uniform
       hw_n = prog->records[r + 1].w[wl];
-      lo_n = 0; hi_n = 0;
-      if (w < 21u && hw_n.field >= 0) {
-        const uint8_t* f = prog->fields[hw_n.field] + 32ull * item;
-        lo_n = (hw_n.q >= 0) ? load_u64(f + 8 * hw_n.q) : 0ull;
-        hi_n = (hw_n.q < 3) ? load_u64(f + 8 * (hw_n.q + 1)) : 0ull;
-      }
+      h_n = { 0ull, 0ull };
+      if (w < 21u) h_n = fetch(prog, hw_n, item);
     }
-    if (w < 21u) {
-      uint64_t v = hw.c;
-      if (hw.field >= 0) {
-        const uint32_t sh = 8u * hw.r;
-        const uint64_t val = sh ? ((lo >> sh) | (hi << (64u - sh))) : lo;
-        v ^= val & hw.fmask;
-      }
-      st = (st & hw.keep) ^ v;
-    }
+    if (w < 21u) st = absorbed(st, hw, h);
 #pragma unroll
     for (int round = 0; round < 24; round++) {   // unrolled: the round constants become literals (a scalar load and its wait a round otherwise)
       // theta: the parity of the column's words inside each DPP row lands on the row's first five lanes (words y = 0, 1, 2 on lanes
@@ -1550,19 +1512,7 @@ __global__ void __launch_bounds__(AFX_BLOCK) k_hash_coop(const afx_hash_program*
       uint32_t xw[16];
 #pragma unroll
       for (int i = 0; i < 8; i++) { const uint64_t t = shfl64(st, (uint32_t)i); xw[2 * i] = (uint32_t)t; xw[2 * i + 1] = (uint32_t)(t >> 32); }
-      if (g == 0u && live) {
-        const sc c = sc_reduce512(xw);
-        uint32_t w8[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) w8[i] = c.v[i];
-        if (rec->squeeze == AFX_SQ_CHALLENGE_COMPARE) {
-          const sc want = sc_load_item(prog->challenge, 32, item);
-          if (!sc_eq(c, want)) atomicOr(&bad[item], AFX_BAD_CHALLENGE);
-          if (prog->trace) enc_store(prog->trace, item, w8);
-        } else {
-          enc_store(prog->outs[rec->squeeze_out], item, w8);
-        }
-      }
+      if (g == 0u && live) release_scalar(prog, rec, xw, bad, item);
     }
   }
   if (prog->save_state && holds && live) prog->save_state[(size_t)w * count + item] = st;
@@ -1608,35 +1558,20 @@ __global__ void __launch_bounds__(AFX_BLOCK) k_hash_coop64(const afx_hash_progra
   const uint32_t nrec = prog->n_records;
   const uint32_t wl = w < 21u ? w : 0u;
   afx_hash_word hw_n = prog->records[0].w[wl];
-  uint64_t lo_n = 0, hi_n = 0;
-  if (w < 21u && hw_n.field >= 0) {
-    const uint8_t* f = prog->fields[hw_n.field] + 32ull * item;
-    lo_n = (hw_n.q >= 0) ? load_u64(f + 8 * hw_n.q) : 0ull;
-    hi_n = (hw_n.q < 3) ? load_u64(f + 8 * (hw_n.q + 1)) : 0ull;
-  }
+  hash_halves h_n = { 0ull, 0ull };
+  if (w < 21u) h_n = fetch(prog, hw_n, item);
 #pragma unroll 1
   for (uint32_t r = 0; r < nrec; r++) {
     const afx_hash_record* rec = &prog->records[r];
     const afx_hash_word hw = hw_n;
-    const uint64_t lo = lo_n, hi = hi_n;
+    const hash_halves h = h_n;
     if (r + 1 < nrec) {   // uniform: the next record's words, requested while this one permutes
       hw_n = prog->records[r + 1].w[wl];
-      lo_n = 0; hi_n = 0;
-      if (w < 21u && hw_n.field >= 0) {
-        const uint8_t* f = prog->fields[hw_n.field] + 32ull * item;
-        lo_n = (hw_n.q >= 0) ? load_u64(f + 8 * hw_n.q) : 0ull;
-        hi_n = (hw_n.q < 3) ? load_u64(f + 8 * (hw_n.q + 1)) : 0ull;
-      }
+      h_n = { 0ull, 0ull };
+      if (w < 21u) h_n = fetch(prog, hw_n, item);
     }
-    if (w < 21u) {
-      uint64_t v = hw.c;
-      if (hw.field >= 0) {
-        const uint32_t sh = 8u * hw.r;
-        const uint64_t val = sh ? ((lo >> sh) | (hi << (64u - sh))) : lo;
-        v ^= val & hw.fmask;
-      }
-      st = (st & half_of(hw.keep)) ^ half_of(v);
-    }
+    // (the step is bitwise: with this lane's half in both halves of the word, half_of takes the lane's half of the result)
+    if (w < 21u) st = half_of(absorbed((uint64_t)st | ((uint64_t)st << 32), hw, h));
 #pragma unroll
     for (int round = 0; round < 24; round++) {
       // theta: column parities as in k_hash_coop, one half each; the rotation by one takes the top bit of the OTHER half's parity
@@ -1663,19 +1598,7 @@ __global__ void __launch_bounds__(AFX_BLOCK) k_hash_coop64(const afx_hash_progra
         xw[2 * i] = (uint32_t)__builtin_amdgcn_ds_bpermute(4 * i, (int)st);
         xw[2 * i + 1] = (uint32_t)__builtin_amdgcn_ds_bpermute(4 * (32 + i), (int)st);
       }
-      if (L == 0u) {
-        const sc c = sc_reduce512(xw);
-        uint32_t w8[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) w8[i] = c.v[i];
-        if (rec->squeeze == AFX_SQ_CHALLENGE_COMPARE) {
-          const sc want = sc_load_item(prog->challenge, 32, item);
-          if (!sc_eq(c, want)) atomicOr(&bad[item], AFX_BAD_CHALLENGE);
-          if (prog->trace) enc_store(prog->trace, item, w8);
-        } else {
-          enc_store(prog->outs[rec->squeeze_out], item, w8);
-        }
-      }
+      if (L == 0u) release_scalar(prog, rec, xw, bad, item);
     }
   }
   if (prog->save_state && holds) {
@@ -1702,18 +1625,14 @@ __global__ void k_fill_u32(const afx_fill_job* __restrict__ jobs, const afx_row*
 }
 // output masking: one grid row per output row, a lane per item; a failed item's 32-byte cell becomes zeros (two 16-byte stores)
 __global__ void __launch_bounds__(AFX_BLOCK) k_mask_rows(const afx_mask_job* __restrict__ jobs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
-  const afx_mask_job job = *row_job(jobs, rows);
-  const afx_pass pass = passes[row_pass_index(rows)];   // wave-uniform: scalar loads
-  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
-  if (item >= pass.count) return;
-  if (pass.bad[item] == 0) return;
+  const auto [job, count, bad, item] = lane_row_of(jobs, rows, passes);
+  if (item >= count) return;
+  if (bad[item] == 0) return;
   uint4* cell = reinterpret_cast<uint4*>(job.p + 32ull * item);
   cell[0] = make_uint4(0u, 0u, 0u, 0u);
   cell[1] = make_uint4(0u, 0u, 0u, 0u);
 }
-__global__ void __launch_bounds__(AFX_BLOCK, 2) k_from_uniform(const uint8_t* __restrict__ wide, uint8_t* __restrict__ out_enc, int32_t* out_var, uint32_t count) {
-  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
-  if (item >= count) return;
+AFX_DEV void from_uniform_item(const uint8_t* wide, uint8_t* out_enc, int32_t* out_var, uint32_t count, uint32_t item) {
   uint32_t w[16];
   enc_load(w, wide, 2 * item);
   enc_load(w + 8, wide, 2 * item + 1);
@@ -1725,9 +1644,7 @@ __global__ void __launch_bounds__(AFX_BLOCK, 2) k_from_uniform(const uint8_t* __
     enc_store(out_enc, item, e);
   }
 }
-__global__ void __launch_bounds__(AFX_BLOCK) k_reduce_wide(const uint8_t* __restrict__ wide, uint8_t* __restrict__ out, uint32_t count) {
-  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
-  if (item >= count) return;
+AFX_DEV void reduce_wide_item(const uint8_t* wide, uint8_t* out, uint32_t item) {
   uint32_t w[16];
   enc_load(w, wide, 2 * item);
   enc_load(w + 8, wide, 2 * item + 1);
@@ -1737,37 +1654,27 @@ __global__ void __launch_bounds__(AFX_BLOCK) k_reduce_wide(const uint8_t* __rest
   for (int i = 0; i < 8; i++) o[i] = r.v[i];
   enc_store(out, item, o);
 }
-// the same two for the launches of a plan: one job per grid row, the row's pass gives the item count
-__global__ void __launch_bounds__(AFX_BLOCK, 2) k_from_uniform_jobs(const afx_uniform_job* __restrict__ jobs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
-  const afx_uniform_job job = *row_job(jobs, rows);
-  const afx_pass pass = passes[row_pass_index(rows)];
-  const uint32_t count = pass.count;
+// the direct forms: the arrays and the item count as kernel arguments
+__global__ void __launch_bounds__(AFX_BLOCK, 2) k_from_uniform(const uint8_t* __restrict__ wide, uint8_t* __restrict__ out_enc, int32_t* out_var, uint32_t count) {
   const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
   if (item >= count) return;
-  uint32_t w[16];
-  enc_load(w, job.wide, 2 * item);
-  enc_load(w + 8, job.wide, 2 * item + 1);
-  const ge_p3 P = ristretto_from_uniform(w);
-  if (job.out_var) var_store(job.out_var, count, item, P);
-  if (job.out_enc) {
-    uint32_t e[8];
-    ristretto_encode(e, P);
-    enc_store(job.out_enc, item, e);
-  }
+  from_uniform_item(wide, out_enc, out_var, count, item);
+}
+__global__ void __launch_bounds__(AFX_BLOCK) k_reduce_wide(const uint8_t* __restrict__ wide, uint8_t* __restrict__ out, uint32_t count) {
+  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
+  if (item >= count) return;
+  reduce_wide_item(wide, out, item);
+}
+// the same two for the launches of a plan: one job per grid row, the row's pass gives the item count
+__global__ void __launch_bounds__(AFX_BLOCK, 2) k_from_uniform_jobs(const afx_uniform_job* __restrict__ jobs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
+  const auto [job, count, bad, item] = lane_row_of(jobs, rows, passes);
+  if (item >= count) return;
+  from_uniform_item(job.wide, job.out_enc, job.out_var, count, item);
 }
 __global__ void __launch_bounds__(AFX_BLOCK) k_reduce_wide_jobs(const afx_reduce_job* __restrict__ jobs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
-  const afx_reduce_job job = *row_job(jobs, rows);
-  const afx_pass pass = passes[row_pass_index(rows)];
-  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
-  if (item >= pass.count) return;
-  uint32_t w[16];
-  enc_load(w, job.wide, 2 * item);
-  enc_load(w + 8, job.wide, 2 * item + 1);
-  const sc r = sc_reduce512(w);
-  uint32_t o[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) o[i] = r.v[i];
-  enc_store(job.out, item, o);
+  const auto [job, count, bad, item] = lane_row_of(jobs, rows, passes);
+  if (item >= count) return;
+  reduce_wide_item(job.wide, job.out, item);
 }
 // decode -> ok flag -> re-encode (round-trip parity test of decode+encode)
 __global__ void __launch_bounds__(AFX_BLOCK, 2) k_validate(const uint8_t* __restrict__ enc, uint8_t* __restrict__ ok, uint8_t* __restrict__ reenc, uint32_t count) {
@@ -1861,10 +1768,8 @@ AFX_DEV void sha512_item(const afx_sha512_job& job, uint32_t item) {
   }
 }
 __global__ void __launch_bounds__(AFX_BLOCK) k_sha512(const afx_sha512_job* __restrict__ jobs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
-  const afx_sha512_job job = *row_job(jobs, rows);
-  const afx_pass pass = passes[row_pass_index(rows)];
-  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
-  if (item >= pass.count) return;
+  const auto [job, count, bad, item] = lane_row_of(jobs, rows, passes);
+  if (item >= count) return;
   sha512_item(job, item);
 }
 // the direct form (afx_sha512): the job as a kernel argument
@@ -1891,10 +1796,8 @@ AFX_DEV void load_msg30(uint32_t mw[8], const uint8_t* m) {
 // tries on average, and a wave waits for its slowest lane).  No counter below 8192 decodes (the reference panics): the item fails,
 // M1, its counter and the rows of the job's other outputs are zeroed.
 __global__ void __launch_bounds__(AFX_BLOCK, 2) k_encode_to_group(const afx_encode_job* __restrict__ jobs, const afx_row* __restrict__ rows, const afx_pass* __restrict__ passes) {
-  const afx_encode_job job = *row_job(jobs, rows);
-  const afx_pass pass = passes[row_pass_index(rows)];
-  const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
-  if (item >= pass.count) return;
+  const auto [job, count, bad, item] = lane_row_of(jobs, rows, passes);
+  if (item >= count) return;
   const uint8_t* m = job.msgs + 30ull * item;
   uint32_t ctr = 0;
   bool found = false;
@@ -1918,7 +1821,7 @@ __global__ void __launch_bounds__(AFX_BLOCK, 2) k_encode_to_group(const afx_enco
     ctr = 0;
 #pragma unroll
     for (int i = 0; i < 8; i++) w[i] = 0;
-    atomicOr(&pass.bad[item], AFX_BAD_DECODE);
+    atomicOr(&bad[item], AFX_BAD_DECODE);
     if (job.zero_a) enc_store(job.zero_a, item, w);
     if (job.zero_b) enc_store(job.zero_b, item, w);
   }
@@ -1929,34 +1832,36 @@ __global__ void __launch_bounds__(AFX_BLOCK, 2) k_encode_to_group(const afx_enco
 // ---------------------------------------------------------------------------------------------
 // host-callable launch wrappers (engine.cpp is plain C++ and never sees a kernel symbol)
 // ---------------------------------------------------------------------------------------------
+#include <type_traits>
 #include "kernels.h"
 // Block size of a plan launch: AFX_BLOCK, but one or two waves when no pass of the launch has more items than that - a launch merged
 // from many small passes (16 items each) then holds one live wave per row instead of a block of four of which three retire at once,
 // and a compute unit keeps twelve such rows in flight instead of three.
 static inline uint32_t block_for(uint32_t max_count) { return max_count <= 64 ? 64u : max_count <= 128 ? 128u : (uint32_t)AFX_BLOCK; }
 static inline dim3 grid_for(uint32_t count, uint32_t njobs) { const uint32_t b = block_for(count); return dim3((count + b - 1) / b, njobs, 1); }
+// The common shape of a plan launch: a lane per item, one job per grid row (`nrows`).
+// `max_count`: the largest item count among the passes of the launch (sizes the grid; a row's lanes past its own pass's count retire)
+template <class K, class... A>
+static hipError_t launch_rows(K kernel, hipStream_t s, uint32_t max_count, uint32_t nrows, A... args) {
+  hipLaunchKernelGGL(kernel, grid_for(max_count, nrows), dim3(block_for(max_count)), 0, s, args...);
+  return hipGetLastError();
+}
 
 hipError_t afxk_setup_generators(hipStream_t s, const uint8_t* enc, uint32_t ngen, int32_t* ext, uint8_t* neg_enc, uint32_t* ok) {
   hipLaunchKernelGGL(k_setup_generators, dim3((ngen + 63) / 64), dim3(64), 0, s, enc, ngen, ext, neg_enc, ok);
   return hipGetLastError();
 }
-// `max_count`: the largest item count among the passes of the launch (sizes the grid; a row's lanes past its own pass's count retire)
 hipError_t afxk_decode(hipStream_t s, const afx_decode_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count, int mixed) {
-  if (mixed) hipLaunchKernelGGL(k_decode_mixed, grid_for(max_count, njobs), dim3(block_for(max_count)), 0, s, jobs, rows, passes);
-  else hipLaunchKernelGGL(k_decode, grid_for(max_count, njobs), dim3(block_for(max_count)), 0, s, jobs, rows, passes);
-  return hipGetLastError();
+  return launch_rows(mixed ? k_decode_mixed : k_decode, s, max_count, njobs, jobs, rows, passes);
 }
 hipError_t afxk_sccheck(hipStream_t s, const afx_sccheck_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) {
-  hipLaunchKernelGGL(k_sccheck, grid_for(max_count, njobs), dim3(block_for(max_count)), 0, s, jobs, rows, passes);
-  return hipGetLastError();
+  return launch_rows(k_sccheck, s, max_count, njobs, jobs, rows, passes);
 }
 hipError_t afxk_pointop(hipStream_t s, const afx_pointop_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) {
-  hipLaunchKernelGGL(k_pointop, grid_for(max_count, njobs), dim3(block_for(max_count)), 0, s, jobs, rows, passes);
-  return hipGetLastError();
+  return launch_rows(k_pointop, s, max_count, njobs, jobs, rows, passes);
 }
 hipError_t afxk_scalarop(hipStream_t s, const afx_scalarop_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) {
-  hipLaunchKernelGGL(k_scalarop, grid_for(max_count, njobs), dim3(block_for(max_count)), 0, s, jobs, rows, passes);
-  return hipGetLastError();
+  return launch_rows(k_scalarop, s, max_count, njobs, jobs, rows, passes);
 }
 // base: scratch for ngen * windows extended points (AFX_VAR_DWORDS each); secret != 0: the 6-bit tables for secret scalars (AFX_SEC_*: a window's 32 multiples, fetched one per lane and exchanged)
 hipError_t afxk_setup_postables(hipStream_t s, const int32_t* ext, uint32_t ngen, int32_t* base, int32_t* postab, int secret) {
@@ -1967,27 +1872,28 @@ hipError_t afxk_setup_postables(hipStream_t s, const int32_t* ext, uint32_t ngen
   hipLaunchKernelGGL(k_setup_postables, dim3((ngen * windows * chunks + 63) / 64), dim3(64), 0, s, base, ngen, postab, windows, entries, wd);
   return hipGetLastError();
 }
+// (encodes, secret) -> the ENC and SEC template arguments of a chain kernel: `f` is called with the two as std::bool_constant values
+template <class F>
+static void with_enc_sec(int encodes, int secret, F f) {
+  if (secret) {
+    if (encodes) f(std::true_type(), std::true_type()); else f(std::false_type(), std::true_type());
+  } else {
+    if (encodes) f(std::true_type(), std::false_type()); else f(std::false_type(), std::false_type());
+  }
+}
 template <int KIND>
 static void launch_msm(hipStream_t s, int encodes, int secret, dim3 grid, dim3 block, const afx_msm_djob* jobs, const int32_t* pos_tables, const int32_t* sec_tables,
                        const afx_pass& P, unsigned long long* clock_probe) {
-  if (secret) {
-    if (encodes) hipLaunchKernelGGL((k_msm<KIND, true, true>), grid, block, 0, s, jobs, pos_tables, sec_tables, P.table_ws, P.digit_ws, P.bad, P.count, clock_probe);
-    else hipLaunchKernelGGL((k_msm<KIND, false, true>), grid, block, 0, s, jobs, pos_tables, sec_tables, P.table_ws, P.digit_ws, P.bad, P.count, clock_probe);
-  } else {
-    if (encodes) hipLaunchKernelGGL((k_msm<KIND, true, false>), grid, block, 0, s, jobs, pos_tables, sec_tables, P.table_ws, P.digit_ws, P.bad, P.count, clock_probe);
-    else hipLaunchKernelGGL((k_msm<KIND, false, false>), grid, block, 0, s, jobs, pos_tables, sec_tables, P.table_ws, P.digit_ws, P.bad, P.count, clock_probe);
-  }
+  with_enc_sec(encodes, secret, [&](auto enc, auto sec) {
+    hipLaunchKernelGGL((k_msm<KIND, decltype(enc)::value, decltype(sec)::value>), grid, block, 0, s, jobs, pos_tables, sec_tables, P.table_ws, P.digit_ws, P.bad, P.count, clock_probe);
+  });
 }
 template <int KIND>
 static void launch_msm_rows(hipStream_t s, int encodes, int secret, dim3 grid, dim3 block, const uint8_t* blob, const int32_t* pos_tables, const int32_t* sec_tables,
                             const afx_row* rows, const afx_pass* passes, unsigned long long* clock_probe) {
-  if (secret) {
-    if (encodes) hipLaunchKernelGGL((k_msm_rows<KIND, true, true>), grid, block, 0, s, blob, pos_tables, sec_tables, rows, passes, clock_probe);
-    else hipLaunchKernelGGL((k_msm_rows<KIND, false, true>), grid, block, 0, s, blob, pos_tables, sec_tables, rows, passes, clock_probe);
-  } else {
-    if (encodes) hipLaunchKernelGGL((k_msm_rows<KIND, true, false>), grid, block, 0, s, blob, pos_tables, sec_tables, rows, passes, clock_probe);
-    else hipLaunchKernelGGL((k_msm_rows<KIND, false, false>), grid, block, 0, s, blob, pos_tables, sec_tables, rows, passes, clock_probe);
-  }
+  with_enc_sec(encodes, secret, [&](auto enc, auto sec) {
+    hipLaunchKernelGGL((k_msm_rows<KIND, decltype(enc)::value, decltype(sec)::value>), grid, block, 0, s, blob, pos_tables, sec_tables, rows, passes, clock_probe);
+  });
 }
 // rows == null: a plan's own launch; `pass_host` is the HOST copy of its pass (the fields travel as kernel arguments).  Otherwise a
 // merged launch: `jobs` is the blob's base, rows / passes are device tables.
@@ -2037,25 +1943,21 @@ hipError_t afxk_msm(hipStream_t s, int kind, int encodes, int secret, const afx_
 }
 hipError_t afxk_msm_tables(hipStream_t s, int kind, const afx_table_job* jobs, uint32_t nrows, const afx_row* rows, const afx_pass* passes, uint32_t max_count) {
   switch (kind) {
-    case TABLE_WINDOW: hipLaunchKernelGGL(k_msm_tables<TABLE_WINDOW>, grid_for(max_count, nrows), dim3(block_for(max_count)), 0, s, jobs, rows, passes); break;
-    case TABLE_ODD: hipLaunchKernelGGL(k_msm_tables<TABLE_ODD>, grid_for(max_count, nrows), dim3(block_for(max_count)), 0, s, jobs, rows, passes); break;
-    case TABLE_NARROW: hipLaunchKernelGGL(k_msm_tables<TABLE_NARROW>, grid_for(max_count, nrows), dim3(block_for(max_count)), 0, s, jobs, rows, passes); break;
-    case TABLE_NARROW_CACHED: hipLaunchKernelGGL(k_msm_tables<TABLE_NARROW_CACHED>, grid_for(max_count, nrows), dim3(block_for(max_count)), 0, s, jobs, rows, passes); break;
+    case TABLE_WINDOW: return launch_rows(k_msm_tables<TABLE_WINDOW>, s, max_count, nrows, jobs, rows, passes);
+    case TABLE_ODD: return launch_rows(k_msm_tables<TABLE_ODD>, s, max_count, nrows, jobs, rows, passes);
+    case TABLE_NARROW: return launch_rows(k_msm_tables<TABLE_NARROW>, s, max_count, nrows, jobs, rows, passes);
+    case TABLE_NARROW_CACHED: return launch_rows(k_msm_tables<TABLE_NARROW_CACHED>, s, max_count, nrows, jobs, rows, passes);
     default: return hipErrorInvalidValue;
   }
-  return hipGetLastError();
 }
 hipError_t afxk_compress2x(hipStream_t s, const afx_compress_job* jobs, const afx_walk_row* rows, uint32_t nrows, const afx_pass* passes, uint32_t max_count) {
-  hipLaunchKernelGGL(k_compress2x, grid_for(max_count, nrows), dim3(block_for(max_count)), 0, s, jobs, rows, passes);
-  return hipGetLastError();
+  return launch_rows(k_compress2x, s, max_count, nrows, jobs, rows, passes);
 }
 hipError_t afxk_table_affine(hipStream_t s, const afx_table_job* jobs, const afx_walk_row* rows, uint32_t nrows, const afx_pass* passes, uint32_t max_count) {
-  hipLaunchKernelGGL(k_table_affine, grid_for(max_count, nrows), dim3(block_for(max_count)), 0, s, jobs, rows, passes);
-  return hipGetLastError();
+  return launch_rows(k_table_affine, s, max_count, nrows, jobs, rows, passes);
 }
 hipError_t afxk_negenc(hipStream_t s, const afx_negenc_job* jobs, const afx_walk_row* rows, uint32_t nrows, const afx_pass* passes, uint32_t max_count) {
-  hipLaunchKernelGGL(k_negenc, grid_for(max_count, nrows), dim3(block_for(max_count)), 0, s, jobs, rows, passes);
-  return hipGetLastError();
+  return launch_rows(k_negenc, s, max_count, nrows, jobs, rows, passes);
 }
 hipError_t afxk_pointsum(hipStream_t s, const afx_pointsum_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count, int many_parts, uint32_t variants) {
   // the idle-device form, under the same rule as k_msm_quad (and the same switch)
@@ -2070,8 +1972,7 @@ hipError_t afxk_pointsum(hipStream_t s, const afx_pointsum_job* jobs, uint32_t n
     hipLaunchKernelGGL(k_pointsum_quad, dim3((max_count + 63) / 64, njobs), dim3(256), 0, s, jobs, rows, passes);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(k_pointsum, grid_for(max_count, njobs), dim3(block_for(max_count)), 0, s, jobs, rows, passes);
-  return hipGetLastError();
+  return launch_rows(k_pointsum, s, max_count, njobs, jobs, rows, passes);
 }
 hipError_t afxk_powers(hipStream_t s, const afx_powers_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) {
   hipLaunchKernelGGL(k_powers_quad, dim3((max_count + 63) / 64, njobs), dim3(256), 0, s, jobs, rows, passes);
@@ -2089,8 +1990,7 @@ hipError_t afxk_hash_coop(hipStream_t s, const afx_hash_program* progs, uint32_t
   return hipGetLastError();
 }
 hipError_t afxk_hash(hipStream_t s, const afx_hash_program* progs, uint32_t nprogs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) {
-  hipLaunchKernelGGL(k_hash, grid_for(max_count, nprogs), dim3(block_for(max_count)), 0, s, progs, rows, passes);
-  return hipGetLastError();
+  return launch_rows(k_hash, s, max_count, nprogs, progs, rows, passes);
 }
 hipError_t afxk_finish(hipStream_t s, const afx_finish_job* jobs, uint32_t njobs, const afx_row* rows, uint32_t max_count) {
   hipLaunchKernelGGL(k_finish, dim3((max_count + 255) / 256, njobs), dim3(256), 0, s, jobs, rows);
@@ -2106,12 +2006,10 @@ hipError_t afxk_fill_u32(hipStream_t s, const afx_fill_job* jobs, uint32_t njobs
   return hipGetLastError();
 }
 hipError_t afxk_from_uniform_jobs(hipStream_t s, const afx_uniform_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) {
-  hipLaunchKernelGGL(k_from_uniform_jobs, grid_for(max_count, njobs), dim3(block_for(max_count)), 0, s, jobs, rows, passes);
-  return hipGetLastError();
+  return launch_rows(k_from_uniform_jobs, s, max_count, njobs, jobs, rows, passes);
 }
 hipError_t afxk_reduce_wide_jobs(hipStream_t s, const afx_reduce_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) {
-  hipLaunchKernelGGL(k_reduce_wide_jobs, grid_for(max_count, njobs), dim3(block_for(max_count)), 0, s, jobs, rows, passes);
-  return hipGetLastError();
+  return launch_rows(k_reduce_wide_jobs, s, max_count, njobs, jobs, rows, passes);
 }
 hipError_t afxk_from_uniform(hipStream_t s, const uint8_t* wide, uint8_t* out_enc, int32_t* out_var, uint32_t count) {
   hipLaunchKernelGGL(k_from_uniform, dim3((count + AFX_BLOCK - 1) / AFX_BLOCK), dim3(AFX_BLOCK), 0, s, wide, out_enc, out_var, count);
@@ -2142,8 +2040,7 @@ hipError_t afxk_draw(hipStream_t s, const afx_draw_job* jobs, uint32_t njobs, ui
   return hipGetLastError();
 }
 hipError_t afxk_sha512_jobs(hipStream_t s, const afx_sha512_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) {
-  hipLaunchKernelGGL(k_sha512, grid_for(max_count, njobs), dim3(block_for(max_count)), 0, s, jobs, rows, passes);
-  return hipGetLastError();
+  return launch_rows(k_sha512, s, max_count, njobs, jobs, rows, passes);
 }
 hipError_t afxk_sha512(hipStream_t s, const uint8_t* src, uint32_t stride, uint32_t offset, uint32_t len, uint8_t* out, uint32_t count) {
   if (!count) return hipSuccess;
@@ -2152,8 +2049,7 @@ hipError_t afxk_sha512(hipStream_t s, const uint8_t* src, uint32_t stride, uint3
   return hipGetLastError();
 }
 hipError_t afxk_encode_to_group(hipStream_t s, const afx_encode_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) {
-  hipLaunchKernelGGL(k_encode_to_group, grid_for(max_count, njobs), dim3(block_for(max_count)), 0, s, jobs, rows, passes);
-  return hipGetLastError();
+  return launch_rows(k_encode_to_group, s, max_count, njobs, jobs, rows, passes);
 }
 
 // whole messages: chunk gather, key-row expansion, per-message status and masking, the candidate at a known counter
