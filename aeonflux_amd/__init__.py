@@ -149,6 +149,22 @@ class BlindRequestGroup(C.Structure):
     _fields_ = [("attrs", AttributesSoA), ("d", C.c_void_p), ("rnd", BlindRequestRandomness), ("count", C.c_size_t)]
 
 
+class TagStatement(C.Structure):
+    """afx_tag_statement (include/aeonflux_gpu.h "Presentation tags"): the position of the hidden scalar and the 32 bytes of the scope
+    generator H, in HOST memory in every form"""
+    _fields_ = [("position", C.c_uint32), ("scope_generator", C.c_char_p)]
+
+
+class TagsSoA(C.Structure):
+    """afx_tags_soa: nonce, T, challenge [count], responses [2][count]"""
+    _fields_ = [(k, C.c_void_p) for k in ("nonce", "T", "challenge", "responses")]
+
+
+class TagsOut(C.Structure):
+    """afx_tags_out: T, challenge [count], responses [2][count]"""
+    _fields_ = [(k, C.c_void_p) for k in ("T", "challenge", "responses")]
+
+
 class CredentialOut(C.Structure):
     """afx_credential_out: t, U, V [total] each, where afx_unblind_issuances_wire writes the credentials"""
     _fields_ = [(k, C.c_void_p) for k in ("t", "U", "V")]
@@ -250,6 +266,16 @@ def lib():
                                                                   C.POINTER(BlindIssueRandomness), C.c_size_t, C.POINTER(BlindIssuanceSoA), C.c_void_p]
                 getattr(_LIB, "afx_unblind_issuances" + sfx).argtypes = [C.c_void_p, C.POINTER(AttributesSoA), C.c_void_p, C.POINTER(BlindRequestSoA),
                                                                         C.POINTER(BlindIssuanceSoA), C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]
+        # (presentation tags: statements_tags.cpp, which the host-simulation builds leave out)
+        if hasattr(_LIB, "afx_show_tagged"):
+            _LIB.afx_tag_scope_generator.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p]
+            for sfx in ("", "_dev"):
+                getattr(_LIB, "afx_show_tagged" + sfx).argtypes = [C.c_void_p, C.POINTER(CredentialsSoA), C.POINTER(KeypairsSoA), C.POINTER(ShowRandomness),
+                                                                  C.POINTER(TagStatement), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(PresentationOut),
+                                                                  C.POINTER(TagsOut), C.POINTER(Shape), C.c_void_p]
+                getattr(_LIB, "afx_verify_presentations_tagged" + sfx).argtypes = [C.c_void_p, C.POINTER(Shape), C.POINTER(PresentationSoA), C.POINTER(TagStatement),
+                                                                                  C.POINTER(TagsSoA), C.c_size_t, C.c_void_p]
+                getattr(_LIB, "afx_verify_tag_proofs" + sfx).argtypes = [C.c_void_p, C.POINTER(TagStatement), C.c_void_p, C.POINTER(TagsSoA), C.c_size_t, C.c_void_p]
         _LIB.afx_wire_header_bytes.restype = C.c_size_t
         _LIB.afx_wire_header_bytes.argtypes = [C.POINTER(Shape)]
         _LIB.afx_wire_cells_per_record.restype = C.c_uint32

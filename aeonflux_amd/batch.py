@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import (AttributesSoA, BlindIssuanceSoA, BlindIssueRandomness, BlindRequestRandomness, BlindRequestSoA, CommitmentsSoA, CredentialsSoA, DeviceRng, EncProofOut, EncProofSoA, IssuanceGroup, IssuanceSoA, IssueGroup, IssueRandomness, KeypairsSoA,
-               PresentationOut, PresentationSoA, Shape, ShowGroup, ShowRandomness, check, lib)
+               PresentationOut, PresentationSoA, Shape, ShowGroup, ShowRandomness, TagsOut, TagsSoA, TagStatement, check, lib)
 
 ENC_FIELDS = ("challenge", "responses", "pk", "E1", "E2", "C_y_1", "C_y_2", "C_y_3", "C_y_2p")
 PRES_FIELDS = ("challenge", "responses", "C_x_0", "C_x_1", "C_V", "C_y", "attr_values")
@@ -667,6 +667,113 @@ def unblind_issuances_dev(ctx, kinds, values, d, request, issuance, n_responses,
     soa = BlindRequestSoA(_dptr(request.get("D")), _dptr(request.get("A")), _dptr(request.get("B")), None, None)
     iss = BlindIssuanceSoA(*(_dptr(issuance.get(f)) for f in BLIND_ISSUANCE_FIELDS))
     check(lib().afx_unblind_issuances_dev(ctx.h, C.byref(a), _dptr(d), C.byref(soa), C.byref(iss), n_responses, count, _dptr(V), _dptr(status)))
+
+
+# ---- presentation tags (include/aeonflux_gpu.h "Presentation tags") -------------------------------------------------------------
+TAG_FIELDS = ("T", "challenge", "responses")
+
+
+def tag_scope_generator(ctx, scope):
+    """afx_tag_scope_generator: H = RistrettoPoint::hash_from_bytes::<Sha512>(scope), 32 bytes"""
+    scope = bytes(scope)
+    out = np.zeros(32, np.uint8)
+    check(lib().afx_tag_scope_generator(ctx.h, scope, len(scope), out.ctypes.data))
+    return bytes(out)
+
+
+def _tag_statement(position, H):
+    H = bytes(H)
+    assert len(H) == 32
+    return TagStatement(position, H)
+
+
+def show_tagged(ctx, kinds, values, t, U, V, keypairs, z_wide, rng_seed, position, H, nonce, tag_seed, enc_seeds=None, M2=None, m3=None):
+    """afx_show_tagged: show() plus the tag of the hidden scalar at `position` under the scope generator H (32 bytes) and the per-item
+    counters nonce [count, 32], its proof drawn from tag_seed [count, 32].
+    Returns (presentation dict, dict(T, challenge [count, 32], responses [2, count, 32]), Shape, status)."""
+    cs, kp, rnd, out, o, cnt, keep = _show_args(kinds, values, t, U, V, keypairs, z_wide, rng_seed, enc_seeds, M2, m3)
+    nonce, tag_seed = _u8(nonce), _u8(tag_seed)
+    tags = dict(T=np.zeros((cnt, 32), np.uint8), challenge=np.zeros((cnt, 32), np.uint8), responses=np.zeros((2, cnt, 32), np.uint8))
+    tout = TagsOut(*(tags[f].ctypes.data for f in TAG_FIELDS))
+    stmt = _tag_statement(position, H)
+    shape = Shape()
+    status = np.full(cnt, 255, np.uint8)
+    check(lib().afx_show_tagged(ctx.h, C.byref(cs), C.byref(kp) if kp is not None else None, C.byref(rnd), C.byref(stmt), nonce.ctypes.data, tag_seed.ctypes.data,
+                                cnt, C.byref(out), C.byref(tout), C.byref(shape), status.ctypes.data))
+    return o, tags, shape, status
+
+
+def tags_soa(nonce, tags, ptr=lambda a: a.ctypes.data):
+    """afx_tags_soa over the counters and a tag dict(T, challenge, responses)"""
+    return TagsSoA(ptr(nonce), *(ptr(tags[f]) for f in TAG_FIELDS))
+
+
+def verify_presentations_tagged(ctx, shape, p, position, H, nonce, tags):
+    """afx_verify_presentations_tagged: p as for verify_presentations, tags as show_tagged returned them -> status [count]"""
+    p = dict(p, **{f: _u8(p[f]) for f in PRES_FIELDS}, enc=[{f: _u8(d[f]) for f in ENC_FIELDS} for d in p["enc"]])
+    cnt = p["challenge"].shape[0]
+    soa, keep = presentation_soa(p)
+    nonce = _u8(nonce)
+    tg = {f: _u8(tags[f]) for f in TAG_FIELDS}
+    ts = tags_soa(nonce, tg)
+    stmt = _tag_statement(position, H)
+    status = np.full(cnt, 255, np.uint8)
+    check(lib().afx_verify_presentations_tagged(ctx.h, C.byref(shape), C.byref(soa), C.byref(stmt), C.byref(ts), cnt, status.ctypes.data))
+    return status
+
+
+def verify_tag_proofs(ctx, position, H, C_y_p, nonce, tags):
+    """afx_verify_tag_proofs: the tag proofs alone on the presentations' C_y[position] row [count, 32] -> status [count]"""
+    C_y_p, nonce = _u8(C_y_p), _u8(nonce)
+    tg = {f: _u8(tags[f]) for f in TAG_FIELDS}
+    cnt = C_y_p.shape[0]
+    ts = tags_soa(nonce, tg)
+    stmt = _tag_statement(position, H)
+    status = np.full(cnt, 255, np.uint8)
+    check(lib().afx_verify_tag_proofs(ctx.h, C.byref(stmt), C_y_p.ctypes.data, C.byref(ts), cnt, status.ctypes.data))
+    return status
+
+
+def show_tagged_dev(ctx, kinds, creds, keypairs, rnd, position, H, nonce, tag_seed, count, out, tags_out, status):
+    """afx_show_tagged_dev over device rows: creds = dict(values, t, U, V[, M2, m3]), keypairs = dict(a, a0, a1, pk) or None, rnd =
+    dict(z_wide, rng_seed[, enc_seeds]), out = a presentation dict of device rows (as presentation_soa reads it), tags_out = dict(T,
+    challenge, responses).  H: 32 bytes of HOST memory.  Returns the Shape."""
+    cs = CredentialsSoA()
+    cs.n_attributes = len(kinds)
+    for i, k in enumerate(kinds):
+        cs.kinds[i] = k
+    for f in ("values", "M2", "m3", "t", "U", "V"):
+        setattr(cs, f, _dptr(creds.get(f)))
+    kp = KeypairsSoA(*(_dptr(keypairs[f]) for f in ("a", "a0", "a1", "pk"))) if keypairs is not None else None
+    r = ShowRandomness(_dptr(rnd["z_wide"]), _dptr(rnd["rng_seed"]), _dptr(rnd.get("enc_seeds")))
+    eouts = (EncProofOut * max(1, len(out["enc"])))()
+    for e, d in enumerate(out["enc"]):
+        for f in ENC_FIELDS:
+            setattr(eouts[e], f, _dptr(d[f]))
+    po = PresentationOut()
+    for f in PRES_FIELDS:
+        setattr(po, f, _dptr(out.get(f)))
+    po.enc = C.cast(eouts, C.POINTER(EncProofOut))
+    tout = TagsOut(*(_dptr(tags_out[f]) for f in TAG_FIELDS))
+    stmt = _tag_statement(position, H)
+    shape = Shape()
+    check(lib().afx_show_tagged_dev(ctx.h, C.byref(cs), C.byref(kp) if kp is not None else None, C.byref(r), C.byref(stmt), _dptr(nonce), _dptr(tag_seed), count,
+                                    C.byref(po), C.byref(tout), C.byref(shape), _dptr(status)))
+    return shape
+
+
+def verify_presentations_tagged_dev(ctx, shape, p, position, H, nonce, tags, count, status):
+    """afx_verify_presentations_tagged_dev: p and tags dicts of device rows"""
+    soa, keep = presentation_soa(p, ptr=_dptr)
+    ts = tags_soa(nonce, tags, ptr=_dptr)
+    stmt = _tag_statement(position, H)
+    check(lib().afx_verify_presentations_tagged_dev(ctx.h, C.byref(shape), C.byref(soa), C.byref(stmt), C.byref(ts), count, _dptr(status)))
+
+
+def verify_tag_proofs_dev(ctx, position, H, C_y_p, nonce, tags, count, status):
+    ts = tags_soa(nonce, tags, ptr=_dptr)
+    stmt = _tag_statement(position, H)
+    check(lib().afx_verify_tag_proofs_dev(ctx.h, C.byref(stmt), _dptr(C_y_p), C.byref(ts), count, _dptr(status)))
 
 
 def multiscalar_mul(ctx, scalars, points):

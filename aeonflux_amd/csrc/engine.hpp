@@ -204,6 +204,12 @@ struct afx_ctx {
     afx::DevBuf weights;             // batchable verification: 256 bytes for the staged seed, then the call's weights [n_weights][count][16]
     void* weights_pin = nullptr;     // pinned image of the 40 seed bytes on their way to `weights` (zeroed once copied)
     hipEvent_t weights_copied = nullptr;
+    afx::DevBuf tags;                // tagged calls (statements_tags.cpp): 256 bytes for the scope generator H (and its validity byte), then the call's
+                                     // [count][32] cells of H and, for a show, its (m + n)^-1 rows (k_tag_broadcast, k_sc_invert)
+    void* tags_pin = nullptr;        // pinned image of H on its way to `tags`, and of the validity byte on its way back
+    afx::Enc tags_H{};               // the H the first 32 bytes of `tags` hold, while tags_H_valid: a call with the same H copies nothing and
+    bool tags_H_valid = false;       // waits for nothing.  Cleared whenever `tags` is replaced (or could not be): a new buffer holds no H
+    hipEvent_t tags_copied = nullptr;
   } lane[5];   // AFX_LANES: large calls alternate between lanes 0 and 1 (host_pipe, pipelining); the coalescer's sessions take whichever is free
   static constexpr int AFX_LANES = 5;
   bool pipelining = false;
@@ -246,6 +252,8 @@ struct afx_ctx {
   bool plan_selfcheck = false;   // AFX_VARIANT_SELFCHECK, or AFX_PLAN_SELFCHECK=1 at context creation (tests): every plan is assembled twice against different
                                  // provisional bases and both relocated copies must be byte-identical - a pointer field the relocation
                                  // does not know shows up as a difference
+  afx::Enc tag_scope_checked{};      // the scope generator the last tagged call found to decode (statements_tags.cpp: a repeated H costs no round trip)
+  bool tag_scope_known = false;
   afx::Session* session = nullptr;   // set while several small calls are being collected into one set of launches (statements.hpp)
   uint32_t n_cu = 256;   // compute units of the device (k_msm keeps 2 blocks resident on each)
   // parity aid (afx_ctx_set_challenge_trace): device array [trace_rows][trace_count][32] receiving every recomputed challenge

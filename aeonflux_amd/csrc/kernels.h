@@ -75,3 +75,10 @@ hipError_t afxk_encode_at(hipStream_t s, const afx_encode_at_job* jobs, uint32_t
 hipError_t afxk_msg_gather(hipStream_t s, const afx_gather_job* job);
 hipError_t afxk_msg_expand(hipStream_t s, const afx_expand_job* job);
 hipError_t afxk_msg_status(hipStream_t s, const afx_msgstat_job* job);
+// presentation tags (tags.cuh, the last part of kernels.hip), direct launches in front of a tagged call's passes: out[i] = (a[i] + b[i])^-1 mod l, or l
+// itself where the sum is 0 ([count][32] each, out 16-byte aligned); rows[i] = the 32 bytes at enc (16-byte aligned).  Weak references
+// on the host side (launch_kinds.hpp).
+hipError_t afxk_sc_invert(hipStream_t s, const uint8_t* a, const uint8_t* b, uint8_t* out, uint32_t count);
+hipError_t afxk_tag_broadcast(hipStream_t s, const uint8_t* enc, uint8_t* rows, uint32_t count);
+// ok[0] = 1 when the 32 bytes at enc decode (the scope generator of a tagged call), else 0
+hipError_t afxk_tag_scope_check(hipStream_t s, const uint8_t* enc, uint8_t* ok);

@@ -2057,3 +2057,6 @@ hipError_t afxk_encode_to_group(hipStream_t s, const afx_encode_job* jobs, uint3
 
 // the coefficient stage of the batchable presentation proofs: its two kernels and their launchers
 #include "batchable.cuh"
+
+// presentation tags: the scalar inversion in front of a tagged call's passes and the broadcast of its scope generator
+#include "tags.cuh"

@@ -17,6 +17,7 @@
 //                                                          afx_keypairs_derive, afx_encrypt and afx_decrypt hash on the host)
 //   afxk_draw                                              fake_draw.cpp (device draws)
 //   afxk_encode_at, afxk_msg_gather / _expand / _status    fake_messages.cpp (whole messages)
+//   afxk_sc_invert, afxk_tag_broadcast, _tag_scope_check   fake_tags.cpp (presentation tags)
 hipError_t afxk_coef(hipStream_t s, const afx_coef_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
 hipError_t afxk_mask_rows(hipStream_t s, const afx_mask_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
 hipError_t afxk_sha512_jobs(hipStream_t s, const afx_sha512_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
@@ -28,6 +29,9 @@ hipError_t afxk_batch_weights(hipStream_t s, const uint8_t* seed, uint64_t index
 hipError_t afxk_msg_gather(hipStream_t s, const afx_gather_job* job) __attribute__((weak));
 hipError_t afxk_msg_expand(hipStream_t s, const afx_expand_job* job) __attribute__((weak));
 hipError_t afxk_msg_status(hipStream_t s, const afx_msgstat_job* job) __attribute__((weak));
+hipError_t afxk_sc_invert(hipStream_t s, const uint8_t* a, const uint8_t* b, uint8_t* out, uint32_t count) __attribute__((weak));
+hipError_t afxk_tag_broadcast(hipStream_t s, const uint8_t* enc, uint8_t* rows, uint32_t count) __attribute__((weak));
+hipError_t afxk_tag_scope_check(hipStream_t s, const uint8_t* enc, uint8_t* ok) __attribute__((weak));
 
 namespace afx {
 
@@ -38,7 +42,8 @@ enum LaunchKind { L_FILL_BAD, L_DECODE, L_SCCHECK, L_POINTOP, L_SCALAROP, L_MSM_
                   L_MSM_FIXED, L_MSM_NAF, L_MSM_TABLES, L_COMPRESS, L_POINTSUM, L_NEGENC, L_TABLE_AFFINE, L_POWERS, L_COEF, L_SHA512, L_ENCODE, L_MASK, L_ENCODE_AT, L_KINDS };
 // Timing slots past the launch kinds: the two cooperative kernels an L_HASH launch may take instead of k_hash (kernels.hip
 // afxk_hash_coop), counted apart so that a test can say which kernel it ran.  "k_hash" (afx_ctx_get_timing) stays the three together.
-enum TimingSlot { T_HASH_COOP = L_KINDS, T_HASH_COOP64, T_SLOTS };
+// T_SC_INVERT: the direct launch in front of a tagged show's passes (statements_tags.cpp), no launch kind of a plan.
+enum TimingSlot { T_HASH_COOP = L_KINDS, T_HASH_COOP64, T_SC_INVERT, T_SLOTS };
 
 // Relocation: a pointer moves with the range it points into (end inclusive: one-past-the-end pointers of empty rows move along)
 struct Mover {
@@ -148,7 +153,7 @@ inline constexpr KindInfo KINDS[] = {
 };
 #undef AFX_COMMON
 #undef AFX_OPTIONAL
-inline constexpr const char* TIMING_SLOT_NAMES[] = { "k_hash_coop", "k_hash_coop64" };   // T_HASH_COOP, T_HASH_COOP64
+inline constexpr const char* TIMING_SLOT_NAMES[] = { "k_hash_coop", "k_hash_coop64", "k_sc_invert" };   // T_HASH_COOP, T_HASH_COOP64, T_SC_INVERT
 
 constexpr bool kinds_in_enum_order() {
   for (int k = 0; k < (int)L_KINDS; k++) if (KINDS[k].kind != k) return false;

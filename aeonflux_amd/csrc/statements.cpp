@@ -271,6 +271,9 @@ extern "C" void afx_ctx_destroy(afx_ctx* c) {
     L.weights.release(true);
     if (L.weights_pin) { memset(L.weights_pin, 0, 64); (void)hipHostFree(L.weights_pin); L.weights_pin = nullptr; }
     if (L.weights_copied) { (void)hipEventDestroy(L.weights_copied); L.weights_copied = nullptr; }
+    L.tags.release(true);
+    if (L.tags_pin) { (void)hipHostFree(L.tags_pin); L.tags_pin = nullptr; }
+    if (L.tags_copied) { (void)hipEventDestroy(L.tags_copied); L.tags_copied = nullptr; }
     if (L.pin) { memset(L.pin, 0, L.pin_cap); (void)hipHostFree(L.pin); L.pin = nullptr; L.pin_cap = 0; }
     if (L.pin_in) { memset(L.pin_in, 0, L.pin_in_cap); (void)hipHostFree(L.pin_in); L.pin_in = nullptr; L.pin_in_cap = 0; }
     if (L.pin_in_done) { (void)hipEventDestroy(L.pin_in_done); L.pin_in_done = nullptr; }
@@ -485,6 +488,48 @@ static void add_encproof_verify(Assembler& as, JobSets& js, uint16_t index, cons
   v.verify_compact(row(e.challenge, 0), trace_row, total, off, js.msm1, js.hash);
 }
 
+// The tag proof of a tagged presentation as a zkp Verifier verifies it (include/aeonflux_gpu.h "Presentation tags"):
+//   C' = C_y[p] + n*G_m[p] = z*G_y[p] + s*G_m[p]   and   H = s*T.
+// Per item: one decoding (T; the cell of H is decoded beside it), one fixed-base job with an addend (C'), two commitment chains
+// (r_z*G_y + r_s*G_m - c*C' and r_s*T - c*H), their encodings and one transcript.  v_Cyp: the decoded C_y[p].  The commitments go to
+// `chains`, a launch behind the one that makes C'.
+static void add_tagproof_verify(Assembler& as, JobSets& js, std::vector<afx_msm_job>& chains, const TagVerify& tv, const int32_t* v_Cyp, size_t total, size_t off,
+                                uint32_t trace_row) {
+  afx_ctx* c = as.ctx;
+  const uint32_t p = tv.position;
+  if (p >= c->n) { as.fail_all = true; return; }   // G_m[p]
+  auto row = [&](const uint8_t* base, size_t k) { return base + (k * total + off) * 32; };
+  js.sccheck.push_back({ row(tv.nonce, 0) });
+  js.sccheck.push_back({ row(tv.challenge, 0) });
+  for (int k = 0; k < 2; k++) js.sccheck.push_back({ row(tv.responses, k) });
+  int32_t *v_T = as.new_var(), *v_H = as.new_var(), *v_Cp = as.new_var();
+  uint8_t* e_Cp = as.new_enc();
+  js.decode.push_back({ row(tv.T, 0), v_T, 1 });
+  js.decode.push_back({ row(tv.H_rows, 0), v_H, 0 });   // (the call refused an H that is the identity encoding or does not decode)
+  afx_msm_job cj;
+  memset(&cj, 0, sizeof cj);
+  set_terms(cj, { mk_term(row(tv.nonce, 0), 32, nullptr, (int32_t)c->id_Gm(p), false) });
+  cj.addend = v_Cyp;
+  cj.out_var = v_Cp;
+  cj.out_enc = e_Cp;
+  cj.reject_identity = 1;
+  js.msm1.push_back(cj);
+  auto resp = [&](int k) { ScalarVar s; s.dev = row(tv.responses, k); s.stride = 32; return s; };
+  SchnorrBuilder v(as, "2019/1416 anonymous credential", "2019/1416 presentation tag proof");
+  const int z = v.allocate_scalar("z", resp(0));
+  const int s = v.allocate_scalar("s", resp(1));
+  const int G_y = v.allocate_point("G_y", PointVar::Const(c->id_Gy(p)));
+  const int G_m = v.allocate_point("G_m", PointVar::Const(c->id_Gm(p)));
+  const int H = v.allocate_point("H", PointVar::Var(v_H, row(tv.H_rows, 0)));
+  const int T = v.allocate_point("T", PointVar::Var(v_T, row(tv.T, 0)));
+  const int Cp = v.allocate_point("C_y+nG_m", PointVar::Var(v_Cp, e_Cp));
+  v.constrain(Cp, { { z, G_y }, { s, G_m } });
+  v.constrain(H, { { s, T } });
+  v.verify_compact(row(tv.challenge, 0), trace_row, total, off, chains, js.hash);
+}
+bool tagged_shape_ok(const afx_ctx* ctx, const afx_shape& shape, uint32_t position) {
+  return position < shape.n_attributes && position < AFX_MAX_ATTRIBUTES && position < ctx->n && shape.kinds[position] == AFX_ENC_SECRET_SCALAR;
+}
 
 // Shapes on which the reference indexes out of range (panics) or zkp rejects every proof: every item fails, and no
 // per-item array is touched.  Also yields the compact C_y list and, per compact index, which hidden-scalar slot
@@ -535,7 +580,7 @@ static bool presentation_shape_rejects(const afx_ctx* c, const afx_shape& sh, ui
 // Issuer::verify -> ProofOfValidCredential::verify, src/nizk/presentation.rs:324-443
 // `bi`: the batchable form (no challenges; commitments and weights instead)
 static void build_presentation_verify(Assembler& as, const afx_shape& sh, const afx_presentation_soa& b, size_t total, size_t off,
-                                      uint8_t* status_dev, BatchableIn* bi = nullptr) {
+                                      uint8_t* status_dev, BatchableIn* bi = nullptr, const TagVerify* tv = nullptr) {
   afx_ctx* c = as.ctx;
   JobSets js;
   auto row = [&](const uint8_t* base, size_t k) { return base + (k * total + off) * 32; };
@@ -543,6 +588,7 @@ static void build_presentation_verify(Assembler& as, const afx_shape& sh, const 
   uint32_t keep[AFX_MAX_ATTRIBUTES], pos[AFX_MAX_ATTRIBUTES], k = 0;
   int hidden_slot[AFX_MAX_ATTRIBUTES];
   if (presentation_shape_rejects(c, sh, keep, &k, hidden_slot, pos)) as.fail_all = true;
+  if (tv && (bi || !tagged_shape_ok(c, sh, tv->position))) as.fail_all = true;   // no hidden scalar at the tag's position: no tag array is read
   if (as.fail_all) { emit(as, js, status_dev, AFX_ST_VERIFICATION_FAILURE); return; }
 
   if (!bi) js.sccheck.push_back({ row(b.challenge, 0) });
@@ -687,11 +733,12 @@ static void build_presentation_verify(Assembler& as, const afx_shape& sh, const 
   if (!expand_Z) js.msm1[z_index].chain_to = (int32_t)first_constraint;
   // proofs of encryption: verified independently, whatever their number (:438-440)
   for (uint32_t e = 0; e < sh.n_enc_proofs && !as.fail_all; e++) add_encproof_verify(as, js, sh.enc_indices[e], b.enc[e], total, off, 1 + e);
+  // the tag proof, on the C_y[p] decoded above: accepted only with the presentation (one status)
+  if (tv && !as.fail_all) add_tagproof_verify(as, js, js.msm2, *tv, v_Cy[tv->position], total, off, 1 + sh.n_enc_proofs);
   emit(as, js, status_dev, AFX_ST_VERIFICATION_FAILURE);
 }
 
-extern "C" int afx_verify_presentations_dev(afx_ctx* ctx, const afx_shape* shape, const afx_presentation_soa* batch, size_t count,
-                                            uint8_t* status_dev) try {
+int verify_presentations_dev_impl(afx_ctx* ctx, const afx_shape* shape, const afx_presentation_soa* batch, size_t count, uint8_t* status_dev, const TagVerify* tag) {
   CtxLock lock__(ctx);
   if (!ctx || !shape || !batch || !status_dev) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   if (!ctx->has_key) { set_error("Issuer::verify needs the issuer key"); return AFX_E_NO_KEY; }
@@ -711,6 +758,7 @@ extern "C" int afx_verify_presentations_dev(afx_ctx* ctx, const afx_shape* shape
         const afx_encproof_soa& q = b.enc[e];
         missing |= !q.challenge || !q.responses || !q.pk || !q.E1 || !q.E2 || !q.C_y_1 || !q.C_y_2 || !q.C_y_3 || !q.C_y_2p;
       }
+      if (tag && tagged_shape_ok(ctx, sh, tag->position)) missing |= !tag->H_rows || !tag->nonce || !tag->T || !tag->challenge || !tag->responses;
       if (missing) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
     }
   }
@@ -718,14 +766,43 @@ extern "C" int afx_verify_presentations_dev(afx_ctx* ctx, const afx_shape* shape
   if (b.enc && sh.n_enc_proofs <= AFX_MAX_ATTRIBUTES) encs.assign(b.enc, b.enc + sh.n_enc_proofs);
   // the plan's size depends on the shape and the mode, not on the arrays: remember it (the trace changes nothing in size,
   // but a too-small trace buffer is a plan error that the sizing run reports, so traced calls are not cached)
+  // (a tagged plan: the position is part of the key; only a host-pointer call's plan is ever kept, and its H cells lie in its staged scratch)
   const afx_shape csh = canonical_shape(sh);
-  const PlanKey key = ctx->trace ? PlanKey() : plan_key("verify_presentations", &csh, sizeof csh, mode_flags(ctx));
+  struct { afx_shape sh; uint32_t p; } kt;
+  memset(&kt, 0, sizeof kt);
+  kt.sh = csh; kt.p = tag ? tag->position : 0;
+  const PlanKey key = ctx->trace ? PlanKey() : tag ? plan_key("verify_presentations_tagged", &kt, sizeof kt, mode_flags(ctx))
+                                                   : plan_key("verify_presentations", &csh, sizeof csh, mode_flags(ctx));
   return run_chunked(ctx, count, [&](Assembler& as, size_t off, uint32_t) {
     afx_presentation_soa bb = b;
     bb.enc = encs.data();
-    build_presentation_verify(as, sh, bb, count, off, status_dev + off);
+    build_presentation_verify(as, sh, bb, count, off, status_dev + off, nullptr, tag);
   }, key);
+}
+extern "C" int afx_verify_presentations_dev(afx_ctx* ctx, const afx_shape* shape, const afx_presentation_soa* batch, size_t count,
+                                            uint8_t* status_dev) try {
+  return verify_presentations_dev_impl(ctx, shape, batch, count, status_dev, nullptr);
 } catch (...) { return afx::exception_rc(); }
+
+// the tag proofs alone (afx_verify_tag_proofs_dev, statements_tags.cpp): the analogue of afx_verify_encryption_proofs_dev; no issuer key
+int verify_tag_proofs_dev_impl(afx_ctx* ctx, const TagVerify& tag, const uint8_t* C_y_p, size_t count, uint8_t* status_dev) {
+  CtxLock lock__(ctx);
+  if (!ctx || !status_dev) { set_error("null argument"); return AFX_E_BAD_ARGS; }
+  if (count == 0) return AFX_OK;
+  if (tag.position < ctx->n && (!C_y_p || !tag.H_rows || !tag.nonce || !tag.T || !tag.challenge || !tag.responses)) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
+  const uint32_t kp = tag.position;
+  const PlanKey key = ctx->trace ? PlanKey() : plan_key("verify_tag_proofs", &kp, sizeof kp, mode_flags(ctx));
+  return run_chunked(ctx, count, [&](Assembler& as, size_t off, uint32_t) {
+    JobSets js;
+    if (tag.position >= as.ctx->n) as.fail_all = true;
+    else {
+      int32_t* v_Cy = as.new_var();
+      js.decode.push_back({ C_y_p + off * 32, v_Cy, 0 });
+      add_tagproof_verify(as, js, js.msm2, tag, v_Cy, count, off, 0);
+    }
+    emit(as, js, status_dev + off, AFX_ST_VERIFICATION_FAILURE);
+  }, key);
+}
 
 // ------------------------------------------------------------------------------------------------
 // batchable presentation proofs: the verifier (include/aeonflux_gpu.h)

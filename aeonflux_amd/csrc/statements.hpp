@@ -250,6 +250,32 @@ int encrypt_on_device(afx_ctx* ctx, const uint8_t* a, const uint8_t* a0, const u
 int decrypt_on_device(afx_ctx* ctx, const uint8_t* a, const uint8_t* a0, const uint8_t* a1, const uint8_t* E1, const uint8_t* E2, size_t count, uint8_t* M1,
                       uint8_t* M2, uint8_t* m3, uint8_t* messages, uint8_t* status);
 
+// Presentation tags (include/aeonflux_gpu.h "Presentation tags"): what a tagged call hands to the show and verify plans - device rows,
+// [count][32] each unless noted.  statements_tags.cpp holds the entry points; it makes H_rows (the call's scope generator in every
+// cell) and inv with direct launches in front of the passes.  The plans themselves live where their untagged twins do, so that every
+// build of statements.cpp and statements_prove.cpp links without that file.
+struct TagShow {
+  uint32_t position;
+  const uint8_t* H_rows;
+  const uint8_t* nonce;        // n, the caller's counter
+  uint8_t* inv;                // (m + n)^-1, or l where m + n == 0 (k_sc_invert); zeroed by the plan
+  const uint8_t* seed;         // what the tag proof's prove_compact draws
+  uint8_t *T, *challenge, *responses;   // outputs; responses [2][count][32]
+};
+struct TagVerify {
+  uint32_t position;
+  const uint8_t* H_rows;
+  const uint8_t *nonce, *T, *challenge, *responses;
+};
+int show_dev_impl(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keypairs_soa* keypairs, const afx_show_randomness* rnd, size_t count,
+                  const afx_presentation_out* out, const afx_commitments_soa* cm, afx_shape* shape_out, uint8_t* status_dev, const TagShow* tag = nullptr);
+// afx_verify_presentations_dev, with the tag proof's verification when `tag` is given (statements.cpp)
+int verify_presentations_dev_impl(afx_ctx* ctx, const afx_shape* shape, const afx_presentation_soa* batch, size_t count, uint8_t* status_dev, const TagVerify* tag);
+// the tag proof alone, on a [count][32] row of received C_y[p] (statements.cpp)
+int verify_tag_proofs_dev_impl(afx_ctx* ctx, const TagVerify& tag, const uint8_t* C_y_p, size_t count, uint8_t* status_dev);
+// does the shape have a hidden scalar at `position`, and would afx_verify_presentations read the batch's arrays at all (statements.cpp)
+bool tagged_shape_ok(const afx_ctx* ctx, const afx_shape& shape, uint32_t position);
+
 struct JobSets {
   std::vector<afx_sccheck_job> sccheck;
   std::vector<afx_decode_job> decode;

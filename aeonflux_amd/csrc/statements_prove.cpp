@@ -240,8 +240,11 @@ extern "C" int afx_issue_dev(afx_ctx* ctx, const afx_attributes_soa* requests, c
 // AnonymousCredential::show
 // ------------------------------------------------------------------------------------------------
 // `cm` (the batchable form, include/aeonflux_gpu.h): the commitments every proof hashed are written out as well
-static int show_dev_impl(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keypairs_soa* keypairs, const afx_show_randomness* rnd,
-                         size_t count, const afx_presentation_out* out, const afx_commitments_soa* cm, afx_shape* shape_out, uint8_t* status_dev) {
+// `tag` (a tagged show, include/aeonflux_gpu.h "Presentation tags"; statements_tags.cpp made its rows): T = (m + n)^-1 * H and its proof
+// are made as well, and every output row of a failed item is zeroed
+int show_dev_impl(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keypairs_soa* keypairs, const afx_show_randomness* rnd,
+                  size_t count, const afx_presentation_out* out, const afx_commitments_soa* cm, afx_shape* shape_out, uint8_t* status_dev,
+                  const TagShow* tag) {
   CtxLock lock__(ctx);
   if (!ctx || !creds || !rnd || !out || !shape_out || !status_dev) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   const afx_credentials_soa cr = *creds;
@@ -249,6 +252,10 @@ static int show_dev_impl(afx_ctx* ctx, const afx_credentials_soa* creds, const a
   if (na == 0 || na > ctx->n) { set_error("credential attribute count does not fit the system parameters"); return AFX_E_BAD_ARGS; }
   for (uint32_t i = 0; i < na; i++)
     if (cr.kinds[i] > AFX_ATTR_SECRET_POINT) { set_error("unknown attribute kind"); return AFX_E_BAD_ARGS; }
+  if (tag && (cm || tag->position >= na || cr.kinds[tag->position] != AFX_ATTR_SECRET_SCALAR)) {
+    set_error("a tag needs the position of a hidden scalar attribute");
+    return AFX_E_BAD_ARGS;
+  }
   // the presentation's shape (encrypted_attributes kinds, hidden_scalar_indices, proofs_of_encryption indices; :293-320)
   afx_shape sh;
   memset(&sh, 0, sizeof sh);
@@ -287,6 +294,7 @@ static int show_dev_impl(afx_ctx* ctx, const afx_credentials_soa* creds, const a
         missing |= !q.challenge || !q.responses || !q.pk || !q.E1 || !q.E2 || !q.C_y_1 || !q.C_y_2 || !q.C_y_3 || !q.C_y_2p;
       }
     }
+    if (tag) missing |= !tag->H_rows || !tag->nonce || !tag->inv || !tag->seed || !tag->T || !tag->challenge || !tag->responses;
     if (missing) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
   }
   const afx_keypairs_soa kp = keypairs ? *keypairs : afx_keypairs_soa{ nullptr, nullptr, nullptr, nullptr };
@@ -297,13 +305,41 @@ static int show_dev_impl(afx_ctx* ctx, const afx_credentials_soa* creds, const a
   struct { uint32_t n; uint8_t kinds[AFX_MAX_ATTRIBUTES]; } kd__;
   memset(&kd__, 0, sizeof kd__);
   kd__.n = na; memcpy(kd__.kinds, cr.kinds, std::min<size_t>(na, AFX_MAX_ATTRIBUTES));
-  const PlanKey key__ = plan_key(cm ? "show_batchable" : "show", &kd__, sizeof kd__, mode_flags(ctx) | (no_key ? 4u : 0u));
+  // (a tagged plan: the position is part of the key.  Only a host-pointer call's plan is ever kept - run_chunked - and that call's H cells and
+  // inverse rows lie in its staged scratch, which the relocation moves; the _dev form's lie in the lane's tag buffer.)
+  struct { uint32_t n, p; uint8_t kinds[AFX_MAX_ATTRIBUTES]; } kt__;
+  memset(&kt__, 0, sizeof kt__);
+  kt__.n = na; kt__.p = tag ? tag->position : 0; memcpy(kt__.kinds, cr.kinds, std::min<size_t>(na, AFX_MAX_ATTRIBUTES));
+  const PlanKey key__ = tag ? plan_key("show_tagged", &kt__, sizeof kt__, mode_flags(ctx) | (no_key ? 4u : 0u))
+                            : plan_key(cm ? "show_batchable" : "show", &kd__, sizeof kd__, mode_flags(ctx) | (no_key ? 4u : 0u));
   return run_chunked(ctx, count, [&](Assembler& as, size_t off, uint32_t cc) {
     afx_ctx* c = as.ctx;
     as.secret_scalars = true;   // z, the hidden attributes, the symmetric key, every blinding: afx_ctx_set_secret_independent_addressing
     auto row = [&](const uint8_t* base, size_t k) { return base + (k * count + off) * 32; };
     auto orow = [&](uint8_t* base, size_t k) { return base + (k * count + off) * 32; };
-    if (no_key) { as.fail_all = true; as.finish(status_dev + off, AFX_ST_NO_SYMMETRIC_KEY); return; }
+    // a tagged show: every output row of the call, for the masking in front of k_finish
+    std::vector<uint8_t*> tag_outs;
+    if (tag) {
+      auto rows_of = [&](uint8_t* base, size_t rows) { for (size_t k = 0; base && k < rows; k++) tag_outs.push_back(orow(base, k)); };
+      rows_of(o.challenge, 1); rows_of(o.responses, 3 + hs); rows_of(o.C_x_0, 1); rows_of(o.C_x_1, 1); rows_of(o.C_V, 1); rows_of(o.C_y, na);
+      for (uint32_t i = 0; i < na; i++)
+        if (cr.kinds[i] != AFX_ATTR_SECRET_SCALAR && cr.kinds[i] != AFX_ATTR_SECRET_POINT && o.attr_values) tag_outs.push_back(orow(o.attr_values, i));
+      for (uint32_t e = 0; e < nsp; e++) {
+        const afx_encproof_out& q = eo[e];
+        rows_of(q.challenge, 1); rows_of(q.responses, 6);
+        for (uint8_t* p : { q.pk, q.E1, q.E2, q.C_y_1, q.C_y_2, q.C_y_3, q.C_y_2p }) rows_of(p, 1);
+      }
+      rows_of(tag->T, 1); rows_of(tag->challenge, 1); rows_of(tag->responses, 2);
+    }
+    if (no_key) {
+      as.fail_all = true;
+      if (tag) {
+        as.wipe(tag->inv + off * 32, 32);   // k_sc_invert has run already
+        as.mask(tag_outs);
+      }
+      as.finish(status_dev + off, AFX_ST_NO_SYMMETRIC_KEY);
+      return;
+    }
     std::vector<afx_sccheck_job> sccheck;
     std::vector<afx_decode_job> decode;
     std::vector<afx_scalarop_job> sc1, sc2;
@@ -322,7 +358,8 @@ static int show_dev_impl(afx_ctx* ctx, const afx_credentials_soa* creds, const a
     for (uint32_t i = 0; i < na; i++) {
       // a commitment that is only a left-hand side of the statement (every C_y of a kind other than a hidden group element)
       // needs no coordinates: the prover never multiplies it.  Without out_var its job is encoded by k_compress2x.
-      v_Cy[i] = cr.kinds[i] == AFX_ATTR_SECRET_POINT ? as.new_var() : nullptr;
+      // (a tagged show adds n*G_m[p] to C_y[p]: that one keeps its coordinates too)
+      v_Cy[i] = (cr.kinds[i] == AFX_ATTR_SECRET_POINT || (tag && i == tag->position)) ? as.new_var() : nullptr;
       std::vector<afx_msm_term> t = { mk_term(z, 32, nullptr, (int32_t)c->id_Gy(i), false) };
       const int32_t* addend = nullptr;
       if (is_scalar_kind(cr.kinds[i])) {
@@ -491,6 +528,36 @@ static int show_dev_impl(afx_ctx* ctx, const afx_credentials_soa* creds, const a
       ep.prove_compact(r.enc_seeds + (e * count + off) * 32, orow(q.challenge, 0), orow(q.responses, 0), 32 * count, rng_hash, commit, chal_hash, resp, &blind_products,
                        cm_main ? R_enc.data() : nullptr);
     }
+    // the tag and its proof (include/aeonflux_gpu.h "Presentation tags"): s = m + n, T = s^-1 * H, C' = C_y[p] + n*G_m[p] (which is
+    // z*G_y[p] + s*G_m[p]: one fixed-base term on the public n and an addend, a stage behind C_y[p]); the proof reuses the presentation's
+    // z, as a proof of encryption does
+    uint8_t* tag_s = nullptr;
+    if (tag) {
+      const uint32_t p = tag->position;
+      const uint8_t *n_row = tag->nonce + off * 32, *H_row = tag->H_rows + off * 32, *inv = tag->inv + off * 32;
+      tag_s = as.new_rows(1);   // zeroed at the end
+      sccheck.push_back({ n_row });
+      sccheck.push_back({ inv });   // l itself where m + n == 0 (k_sc_invert): the item fails
+      sc1.push_back(mk_scalarop(c->const_one(), 0, n_row, 32, row(cr.values, p), 32, false, tag_s));
+      int32_t *v_H = as.new_var(), *v_T = as.new_var();
+      uint8_t* e_Cp = as.new_enc();
+      decode.push_back({ H_row, v_H, 0 });
+      msm1.push_back(mk_job({ mk_term(inv, 32, v_H, -1, false) }, nullptr, v_T, tag->T + off * 32, true));
+      msm1b.push_back(mk_job({ mk_term(n_row, 32, nullptr, (int32_t)c->id_Gm(p), false) }, v_Cy[p], nullptr, e_Cp, true));
+      SchnorrBuilder tp(as, "2019/1416 anonymous credential", "2019/1416 presentation tag proof");
+      const int tz = tp.allocate_scalar("z", sv_item(z));
+      const int ts = tp.allocate_scalar("s", sv_item(tag_s));
+      const int tG_y = tp.allocate_point("G_y", PointVar::Const(c->id_Gy(p)));
+      const int tG_m = tp.allocate_point("G_m", PointVar::Const(c->id_Gm(p)));
+      const int tH = tp.allocate_point("H", PointVar::Var(v_H, H_row));
+      PointVar pT = PointVar::Var(v_T, tag->T + off * 32);
+      pT.parts.push_back({ inv, 32, false, v_H, -1 });   // T = s^-1 * H (a segmenting pass multiplies by H instead: SchnorrBuilder::prove_compact)
+      const int tT = tp.allocate_point("T", pT);
+      const int tCp = tp.allocate_point("C_y+nG_m", PointVar::Var(nullptr, e_Cp));   // a left-hand side only
+      tp.constrain(tCp, { { tz, tG_y }, { ts, tG_m } });
+      tp.constrain(tH, { { ts, tT } });
+      tp.prove_compact(tag->seed + off * 32, tag->challenge + off * 32, tag->responses + off * 32, 32 * count, rng_hash, commit, chal_hash, resp, &blind_products);
+    }
     as.sccheck(sccheck);
     as.decode(decode);
     as.scalarop(sc1);
@@ -503,6 +570,11 @@ static int show_dev_impl(afx_ctx* ctx, const afx_credentials_soa* creds, const a
     as.msm(commit);
     as.hash(chal_hash);
     as.scalarop(resp);
+    if (tag) {
+      as.wipe(tag_s, 32);
+      as.wipe(tag->inv + off * 32, 32);
+      as.mask(tag_outs);
+    }
     as.finish(status_dev + off, AFX_ST_VERIFICATION_FAILURE);
   }, key__);
 }

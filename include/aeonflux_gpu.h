@@ -937,6 +937,98 @@ int afx_unblind_issuances(afx_ctx* ctx, const afx_attributes_soa* attrs, const u
 int afx_unblind_issuances_dev(afx_ctx* ctx, const afx_attributes_soa* attrs, const uint8_t* d, const afx_blind_request_soa* requests,
                               const afx_blind_issuance_soa* issuances, uint32_t n_responses, size_t count, uint8_t* V, uint8_t* status_dev);
 
+/* ---- Presentation tags: rate-limited shows with a per-scope pseudonym -------------------------
+ * A presentation is unlinkable and afx_show takes no nonce or counter: nothing stops one credential from being shown a million times.
+ * A TAGGED presentation also carries T = (m + n)^-1 * H, where m is a hidden scalar attribute of the credential, n a public per-item
+ * counter and H a public generator that names the scope, with a proof that T was made from the attribute the MAC covers.  T is a
+ * function of (attribute, n, scope) alone: a second show under the same counter and scope gives the same 32 bytes, shows under another
+ * scope cannot be linked to it.  "At most N shows per credential and scope" is then the verifier's rule n < N on its own public rows plus
+ * a set lookup on T.  (CMZ'14 MAC_GGM with a Dodis-Yampolskiy style tag, as the IETF ARC draft does.)  The crate has no counterpart.
+ * Off unless called: nothing above changes.
+ *
+ * Protocol (normative).  p = the tag's position, whose credential kind is AFX_ATTR_SECRET_SCALAR; H = the scope generator, 32 bytes, one
+ * per call; n = the item's counter, a canonical scalar (the library requires nothing else of it: enforcing n < limit is the caller's
+ * policy); m = values[p].
+ *
+ * Scope generator.  afx_tag_scope_generator computes H = RistrettoPoint::from_uniform_bytes(SHA-512(scope)), dalek's
+ * hash_from_bytes::<Sha512>, for a scope of 0 .. 1024 bytes.  A caller may pass any H; the soundness of the link between T and the
+ * attribute, and unlinkability across scopes, need an H whose discrete logarithms to the system generators and to other scopes' H are
+ * unknown.  Every call refuses an H that does not decode, or whose encoding is 32 zero bytes, with AFX_E_BAD_ARGS.
+ *
+ * 1. Show (user).  Everything afx_show does, byte for byte, from the same z_wide, rng_seed and enc_seeds.  In addition, per item,
+ *      s = m + n mod l,   T = s^-1 * H,   C' = C_y[p] + n*G_m[p]  ( = z*G_y[p] + s*G_m[p] )
+ *    and a compact proof under Transcript::new(b"2019/1416 anonymous credential") and the label "2019/1416 presentation tag proof":
+ *      scalars      "z" (the presentation's z), "s"
+ *      points       "G_y" = G_y[p], "G_m" = G_m[p], "H", "T", "C_y+nG_m" = C'
+ *      constraints  C' = z*G_y + s*G_m;   H = s*T
+ *    whose prove_compact draws from tag_seed[item].  Outputs: T, the challenge, two responses in the order (z, s).  An item whose n is
+ *    not canonical, whose s is 0, or which fails afx_show itself fails with AFX_ST_VERIFICATION_FAILURE, and
+ *    AN ITEM THAT FAILS GETS ZEROS IN EVERY OUTPUT ROW OF THE CALL - the presentation's rows included - written on the device
+ *    (k_mask_rows, in front of k_finish) before the call completes.
+ * 2. Verify (issuer).  status = AFX_ST_OK iff afx_verify_presentations accepts the presentation unchanged AND the tag proof verifies as a
+ *    zkp Verifier verifies it: n, the challenge and both responses canonical, T decodes, neither T nor C' (computed from the received
+ *    C_y[p]) encodes to 32 zero bytes, the recomputed challenge equals the received one.  A shape whose kinds[p] is not
+ *    AFX_ENC_SECRET_SCALAR, or with p >= n_attributes, fails every item and no tag array is read.  The tag proof does not depend on
+ *    strict mode; where the crate's constraint-#3 behaviour rejects honest presentations of a shape, the combined status rejects them too.
+ *    afx_verify_tag_proofs is the analogue of afx_verify_encryption_proofs: the tag proof alone, on a row of received C_y[p]; any context.
+ *
+ * Why T is bound to the credential.  Constraint 1 extracts (z', s) with C_y[p] = z'*G_y[p] + (s - n)*G_m[p]; the presentation proof
+ * extracts (z, m) for the same C_y[p]; binding under the discrete logarithm between G_y[p] and G_m[p] gives s = m + n; constraint 2
+ * then fixes T = (m + n)^-1 * H.  Detecting equal T is the caller's set lookup: the library keeps no store of tags.
+ *
+ * Secrets.  m, s and s^-1: the show is a prover-side plan under the context's secret-independent addressing like afx_show; s^-1 is made
+ * by a kernel whose instruction stream and addresses do not depend on s (Fermat's inverse over the bits of the public l - 2), and the
+ * rows that hold s and s^-1 are zeroed on the device, in stream order, before the call completes.  Verification is a public plan, as
+ * afx_verify_presentations in each mode.
+ *
+ * Conventions.  `scope_generator` is a HOST pointer in every form, `_dev` included, read before the call returns.  The host-pointer
+ * forms take the context in turn (they join no collecting session) and stage a call in one piece; counts beyond
+ * afx_ctx_set_chunk_items run as several passes; small ones keep their plans like the other host-pointer calls (a plan-cache key of their
+ * own, which holds the position).  `_dev`: every other pointer a device pointer, rows 16-byte aligned, the call asynchronous on
+ * afx_ctx_stream with one exception: a call whose H is not the one its lane's buffer already holds waits for the work queued on that
+ * stream (the copy of H leaves a pinned image; a new H also has its decoding read back).  Calls that repeat a scope - the usual case -
+ * copy nothing and wait for nothing from the second call on each lane on (with afx_ctx_set_pipelining calls alternate between two lanes,
+ * each of which copies H once), until a call needs a larger buffer: the buffer that replaces it receives H again.
+ * Out of scope: a wire format for tagged presentations, afx_group_* forms, _rng draws of tag_seed, the batchable encoding of the tag
+ * proof, mixed layouts and coalescing, the Rust shim, bench.py, any duplicate-tag store. */
+/* (declared apart from their typedefs, like afx_device_rng: the Rust shim does not bind them) */
+struct afx_tag_statement {
+  uint32_t position;               /* p                                            */
+  const uint8_t* scope_generator;  /* H, 32 bytes, HOST memory in every form       */
+};
+typedef struct afx_tag_statement afx_tag_statement;
+struct afx_tags_soa {              /* a batch of received tags                     */
+  const uint8_t* nonce;            /* [count] Sc     n                             */
+  const uint8_t* T;                /* [count] Pt                                   */
+  const uint8_t* challenge;        /* [count] Sc                                   */
+  const uint8_t* responses;        /* [2][count] Sc  (z, s)                        */
+};
+typedef struct afx_tags_soa afx_tags_soa;
+struct afx_tags_out {              /* written by afx_show_tagged                   */
+  uint8_t* T;                      /* [count] Pt                                   */
+  uint8_t* challenge;              /* [count] Sc                                   */
+  uint8_t* responses;              /* [2][count] Sc                                */
+};
+typedef struct afx_tags_out afx_tags_out;
+/* scope: scope_len bytes (0 .. 1024; may be NULL when 0).  Any context.  A cold-path helper: two calls of count 1. */
+int afx_tag_scope_generator(afx_ctx* ctx, const uint8_t* scope, size_t scope_len, uint8_t out[32]);
+/* as afx_show; nonce: [count] Sc; tag_seed: [count][32].  A position that is no hidden scalar of the credentials: AFX_E_BAD_ARGS. */
+int afx_show_tagged(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keypairs_soa* keypairs, const afx_show_randomness* rnd,
+                    const afx_tag_statement* tag, const uint8_t* nonce, const uint8_t* tag_seed, size_t count, const afx_presentation_out* out,
+                    const afx_tags_out* tags_out, afx_shape* shape_out, uint8_t* status);
+int afx_show_tagged_dev(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keypairs_soa* keypairs, const afx_show_randomness* rnd,
+                        const afx_tag_statement* tag, const uint8_t* nonce, const uint8_t* tag_seed, size_t count, const afx_presentation_out* out,
+                        const afx_tags_out* tags_out, afx_shape* shape_out, uint8_t* status_dev);
+/* as afx_verify_presentations (needs the issuer key) */
+int afx_verify_presentations_tagged(afx_ctx* ctx, const afx_shape* shape, const afx_presentation_soa* batch, const afx_tag_statement* tag,
+                                    const afx_tags_soa* tags, size_t count, uint8_t* status);
+int afx_verify_presentations_tagged_dev(afx_ctx* ctx, const afx_shape* shape, const afx_presentation_soa* batch, const afx_tag_statement* tag,
+                                        const afx_tags_soa* tags, size_t count, uint8_t* status_dev);
+/* C_y_p: [count] Pt, the presentations' C_y[p].  A position >= the context's n fails every item. */
+int afx_verify_tag_proofs(afx_ctx* ctx, const afx_tag_statement* tag, const uint8_t* C_y_p, const afx_tags_soa* tags, size_t count, uint8_t* status);
+int afx_verify_tag_proofs_dev(afx_ctx* ctx, const afx_tag_statement* tag, const uint8_t* C_y_p, const afx_tags_soa* tags, size_t count,
+                              uint8_t* status_dev);
+
 /* ---- Blind issuance on bytes: AFXQ requests in, AFXJ issuances out ----------------------------
  * The issuer's side of the section above with the two doors the plain issuer has (afx_issue_wire, afx_issue_wire_rng): serialized
  * records, and randomness drawn on the device, over one context or a group.  Off unless called: nothing above changes.  H, h, hs as
