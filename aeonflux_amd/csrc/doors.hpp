@@ -1,7 +1,9 @@
-// What the entry points that take bytes in and give bytes out (the "doors": wire_issue.cpp, wire_user.cpp, wire_blind.cpp) and the
-// calls over several groups or devices (mixed.cpp, group.cpp) share on the host: little-endian words, the scheduling of a request's
-// batches on one context, and one host thread per member of a group.  A header, not a source file: the host simulations under tests/
-// keep their own source lists.
+// What the entry points that take bytes in and give bytes out (the "doors": wire.cpp, wire_issue.cpp, wire_user.cpp, wire_batchable.cpp,
+// wire_blind.cpp, wire_blind_user.cpp) and the calls over several groups or devices (mixed.cpp, group.cpp) share on the host:
+// little-endian words, the scheduling of a request's batches on one context, and one host thread per member of a group.  What a
+// format's header looks like is wire_formats.hpp's (which includes this), the transposition of records on the GPU is records.hpp's,
+// the splitting of a request stream request_stream.hpp's.  A header, not a source file: the host simulations under tests/ keep their
+// own source lists.
 #pragma once
 #include <memory>
 #include <string>

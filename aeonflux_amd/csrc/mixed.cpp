@@ -7,7 +7,7 @@
 #include <memory>
 #include <string>
 #include <vector>
-#include "doors.hpp"
+#include "wire_formats.hpp"
 
 namespace {
 
@@ -249,51 +249,49 @@ extern "C" int afx_group_show_mixed(afx_group* group, afx_show_group* groups, si
   return rc;
 } catch (...) { return afx::exception_rc(); }
 
-extern "C" int afx_wire_section_bytes(const uint8_t* blob, size_t len, size_t* section_len_out) try {
-  if (!blob || !section_len_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  if (len < 32 || memcmp(blob, "AFXP", 4) != 0 || rd32(blob + 4) != 1) { set_error("not an AFXP v1 section"); return AFX_E_BAD_ARGS; }
-  const uint64_t count = rd32(blob + 8), cells = rd32(blob + 12);
-  const uint32_t n = rd32(blob + 16), nr = rd32(blob + 20), hs = rd32(blob + 24), ne = rd32(blob + 28);
-  if (n > AFX_MAX_ATTRIBUTES || nr > 3 + AFX_MAX_ATTRIBUTES || hs > AFX_MAX_ATTRIBUTES || ne > AFX_MAX_ATTRIBUTES) { set_error("shape field out of range"); return AFX_E_BAD_ARGS; }
-  const size_t hdr = (32 + (size_t)n + 2 * (size_t)hs + 2 * (size_t)ne + 31) & ~size_t(31);
-  if (cells > 4 + 3 * (uint64_t)AFX_MAX_ATTRIBUTES + 14 * (uint64_t)AFX_MAX_ATTRIBUTES + 3) { set_error("cells_per_record out of range"); return AFX_E_BAD_ARGS; }
-  const uint64_t total = (uint64_t)hdr + count * cells * 32;   // < 2^32 * 2^10 * 2^5: no overflow
-  if (total > len) { set_error("section runs past the end of the blob"); return AFX_E_BAD_ARGS; }
-  *section_len_out = (size_t)total;
+namespace {
+// An AFXP stream split into its sections (every one read in full: a malformed one anywhere fails the call before anything runs),
+// grouped by the used part of the shape
+struct Section { size_t off, len, hdr, count, first; };
+struct Group { std::vector<Section> sections; size_t count = 0; };
+struct Sections {
+  std::map<std::string, Group> by_shape;
+  std::vector<std::string> order;   // groups in order of first appearance
+  size_t total = 0;
+};
+int split_stream(const uint8_t* blob, size_t len, Sections& S) {
+  for (size_t off = 0; off < len;) {
+    Header H;
+    const int rc = read_section(FORMATS[AFXP], blob + off, len - off, H);
+    if (rc) { set_error("section at byte " + std::to_string(off) + ": " + afx_last_error()); return rc; }
+    const std::string key = shape_key(shape_of(H));
+    auto it = S.by_shape.find(key);
+    if (it == S.by_shape.end()) { it = S.by_shape.emplace(key, Group()).first; S.order.push_back(key); }
+    it->second.sections.push_back({ off, H.section, H.hdr, H.count, S.total });
+    it->second.count += H.count;
+    S.total += H.count;
+    off += H.section;
+  }
   return AFX_OK;
-} catch (...) { return afx::exception_rc(); }
+}
+}  // namespace
 
 // `verify_section(section bytes, length, status, cap, &n)`: one same-shape AFXP batch on a context or on a group of them
 // (one context; the group form below deals the shape groups out to its members)
 template <class VerifySection>
 static int mixed_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, uint8_t* status, size_t status_cap, size_t* count_out, VerifySection&& verify_section) {
   if ((!blob && len) || !count_out || (!status && status_cap)) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  struct Section { size_t off, len, hdr, count, first; };
-  struct Group { std::vector<Section> sections; size_t count = 0; };
-  std::map<std::string, Group> by_shape;
-  std::vector<std::string> order;   // groups in order of first appearance
-  size_t total = 0;
-  for (size_t off = 0; off < len;) {
-    size_t sl = 0;
-    int rc = afx_wire_section_bytes(blob + off, len - off, &sl);
-    if (rc) { set_error("section at byte " + std::to_string(off) + ": " + afx_last_error()); return rc; }
-    afx_shape sh;
-    size_t cnt = 0, rec = 0;
-    if ((rc = afx_wire_parse(blob + off, sl, &sh, &cnt, &rec))) { set_error("section at byte " + std::to_string(off) + ": " + afx_last_error()); return rc; }
-    const std::string key = shape_key(sh);
-    auto it = by_shape.find(key);
-    if (it == by_shape.end()) { it = by_shape.emplace(key, Group()).first; order.push_back(key); }
-    it->second.sections.push_back({ off, sl, rec, cnt, total });
-    it->second.count += cnt;
-    total += cnt;
-    off += sl;
-  }
+  Sections split;
+  int rc = split_stream(blob, len, split);
+  if (rc) return rc;
+  std::map<std::string, Group>& by_shape = split.by_shape;
+  const std::vector<std::string>& order = split.order;
+  const size_t total = split.total;
   *count_out = total;
   if (total > status_cap) { set_error("status buffer too small"); return AFX_E_BAD_ARGS; }
   // with a context: the small groups are collected and run as one set of launches (see run_groups)
   std::unique_ptr<CtxLock> lock;
   std::unique_ptr<afx::Session> ses;
-  int rc = AFX_OK;
   // (as in run_groups: with the collector on, the stream's shape groups join the collecting session)
   afx::Deferred deferred;
   std::unique_ptr<afx::DeferScope> defer;
@@ -385,26 +383,11 @@ extern "C" int afx_group_verify_presentations_mixed_wire(afx_group* group, const
   if ((!blob && len) || !count_out || (!status && status_cap)) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   const uint32_t m = afx_group_size(group);
   if (m == 0) { set_error("empty group"); return AFX_E_BAD_ARGS; }
-  struct Section { size_t off, len, hdr, count, first; };
-  struct Group { std::vector<Section> sections; size_t count = 0; };
-  std::map<std::string, Group> by_shape;
-  std::vector<std::string> order;   // groups in order of first appearance
-  size_t total = 0;
-  for (size_t off = 0; off < len;) {
-    size_t sl = 0;
-    int rc = afx_wire_section_bytes(blob + off, len - off, &sl);
-    if (rc) { set_error("section at byte " + std::to_string(off) + ": " + afx_last_error()); return rc; }
-    afx_shape sh;
-    size_t cnt = 0, rec = 0;
-    if ((rc = afx_wire_parse(blob + off, sl, &sh, &cnt, &rec))) { set_error("section at byte " + std::to_string(off) + ": " + afx_last_error()); return rc; }
-    const std::string key = shape_key(sh);
-    auto it = by_shape.find(key);
-    if (it == by_shape.end()) { it = by_shape.emplace(key, Group()).first; order.push_back(key); }
-    it->second.sections.push_back({ off, sl, rec, cnt, total });
-    it->second.count += cnt;
-    total += cnt;
-    off += sl;
-  }
+  Sections split;
+  if (const int rc = split_stream(blob, len, split)) return rc;
+  std::map<std::string, Group>& by_shape = split.by_shape;
+  const std::vector<std::string>& order = split.order;
+  const size_t total = split.total;
   *count_out = total;
   if (total > status_cap) { set_error("status buffer too small"); return AFX_E_BAD_ARGS; }
   const uint32_t small = afx_group_small_batch_items(group);

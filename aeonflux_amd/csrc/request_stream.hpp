@@ -3,47 +3,12 @@
 // answer gets its header, the batches run - on one context or split over a group's members - and what was gathered goes back to its
 // sections.  The two doors differ in data only: a Door says what a format's sections look like, how large its records are, which
 // randomness a request takes and which function runs a batch's items.  Only bytes move here; what is staged and launched is the
-// doors' own (issue_records, run_records).
+// doors' own (issue_records, run_records), and what a header looks like is wire_formats.hpp's.
 #pragma once
 #include <map>
-#include "doors.hpp"
+#include "wire_formats.hpp"
 
 namespace {   // (every source file its own copy, as before: nothing here is exported from the library)
-
-inline bool is_hidden_kind(uint8_t k) { return k == AFX_ATTR_SECRET_SCALAR || k == AFX_ATTR_SECRET_POINT; }
-
-// h and hs of a layout (kinds already checked to be in range)
-struct Hidden { uint32_t h = 0, hs = 0; };
-inline Hidden hidden_of(const uint8_t* kinds, uint32_t n) {
-  Hidden r;
-  for (uint32_t i = 0; i < n; i++) {
-    r.h += is_hidden_kind(kinds[i]);
-    r.hs += kinds[i] == AFX_ATTR_SECRET_SCALAR;
-  }
-  return r;
-}
-
-// The header AFXI, AFXQ and AFXJ share: magic | version | count | cells_per_record | n_attributes | n_responses | kinds | padding.
-inline size_t header_bytes(uint32_t n) { return n > AFX_MAX_ATTRIBUTES ? 0 : (24 + (size_t)n + 31) & ~size_t(31); }
-inline void write_header(uint8_t* h, const char* magic, size_t hdr, size_t count, uint32_t cells, uint32_t n, uint32_t nr, const uint8_t* kinds) {
-  memset(h, 0, hdr);
-  memcpy(h, magic, 4);
-  wr32(h + 4, 1); wr32(h + 8, (uint32_t)count); wr32(h + 12, cells); wr32(h + 16, n); wr32(h + 20, nr);
-  memcpy(h + 24, kinds, n);
-}
-struct Header { uint32_t count, cells, n, nr; size_t hdr; };
-inline int read_header(const uint8_t* blob, size_t len, const char* magic, Header& H) {
-  if (len < 24 || memcmp(blob, magic, 4) != 0 || rd32(blob + 4) != 1) { set_error(std::string("not an ") + magic + " v1 section"); return AFX_E_BAD_ARGS; }
-  H.count = rd32(blob + 8); H.cells = rd32(blob + 12); H.n = rd32(blob + 16); H.nr = rd32(blob + 20);
-  if (H.n > AFX_MAX_ATTRIBUTES) { set_error("n_attributes out of range"); return AFX_E_BAD_ARGS; }
-  H.hdr = header_bytes(H.n);
-  if (len < H.hdr) { set_error("truncated header"); return AFX_E_BAD_ARGS; }
-  for (uint32_t i = 0; i < H.n; i++)
-    if (blob[24 + i] > AFX_ATTR_SECRET_POINT) { set_error("attribute kind out of range"); return AFX_E_BAD_ARGS; }
-  for (size_t k = 24 + (size_t)H.n; k < H.hdr; k++)   // (the padding is part of the format: a section that parses packs to the same bytes)
-    if (blob[k]) { set_error("header padding is not zero"); return AFX_E_BAD_ARGS; }
-  return AFX_OK;
-}
 
 // One request section of a stream and where its answer goes in `out`.
 struct Section {
@@ -78,10 +43,7 @@ struct Stream {
 
 // What tells one door from the other.
 struct Door {
-  const char* out_magic;                                          // "AFXI" or "AFXJ"
-  // the input format: a section's length, and its layout, count and the offset of its records (nrq_out: see Section)
-  int (*section_bytes)(const uint8_t* blob, size_t len, size_t* section_len_out);
-  int (*parse)(const uint8_t* blob, size_t len, uint32_t* n_out, uint8_t* kinds_out, uint32_t* nrq_out, size_t* count_out, size_t* rec_out);
+  const Format *in, *out;                                         // (wire_formats.hpp) AFXR in, AFXI out; or AFXQ in, AFXJ out
   uint32_t (*cells_in)(uint32_t n, uint32_t h, uint32_t hs);      // cells of a request record of a layout
   uint32_t (*cells_out)(uint32_t n, uint32_t ctx_n);              // cells of an answer record to a section of n attributes
   uint32_t (*n_responses)(uint32_t ctx_n);                        // of the answer's proof
@@ -103,14 +65,17 @@ inline int parse_stream(const Door& d, const uint8_t* blob, size_t len, uint32_t
   if (!blob && len) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   std::map<std::string, size_t> by_layout;
   for (size_t off = 0; off < len;) {
-    size_t sl = 0, cnt = 0, rec = 0;
-    Section s;
-    int rc = d.section_bytes(blob + off, len - off, &sl);
-    if (!rc) rc = d.parse(blob + off, sl, &s.n, s.kinds, &s.nrq, &cnt, &rec);
+    Header H;
+    const int rc = read_section(*d.in, blob + off, len - off, H);
     if (rc) { set_error("section at byte " + std::to_string(off) + ": " + afx_last_error()); return rc; }
-    s.off = off; s.hdr = rec; s.count = cnt; s.first = S.total;
+    const size_t cnt = H.count;
+    Section s;
+    s.off = off; s.hdr = H.hdr; s.count = cnt; s.first = S.total;
+    s.n = H.n; s.nrq = H.nr;
+    memset(s.kinds, 0, sizeof s.kinds);
+    memcpy(s.kinds, H.kinds, H.n);
     s.out_off = S.out_len;
-    s.out_hdr = header_bytes(s.n);
+    s.out_hdr = header_bytes(*d.out, s.n);
     const size_t out_bytes = s.out_hdr + cnt * d.cells_out(s.n, ctx_n) * 32;   // (< 2^32 * 2^7 * 2^5)
     if (__builtin_add_overflow(S.out_len, out_bytes, &S.out_len) || __builtin_add_overflow(S.total, cnt, &S.total)) {
       set_error("request stream too large");
@@ -131,7 +96,7 @@ inline int parse_stream(const Door& d, const uint8_t* blob, size_t len, uint32_t
       S.batches[it->second].count += cnt;
     }
     S.secs.push_back(s);
-    off += sl;
+    off += H.section;
   }
   return AFX_OK;
 }
@@ -159,7 +124,7 @@ inline void prepare(Stream& S, const Door& d, const uint8_t* blob, const uint8_t
     if (d.issue) {
       const uint32_t out_cells = d.cells_out(s.n, ctx_n);
       uint8_t* h = out + s.out_off;
-      write_header(h, d.out_magic, s.out_hdr, s.count, out_cells, s.n, nr, s.kinds);
+      write_header(*d.out, h, s.count, out_cells, s.n, nr, s.kinds);
       if (!on_gpu) memset(h + s.out_hdr, 0, s.count * out_cells * 32);
     }
     if (!on_gpu) memset(status + s.first, d.foreign_status, s.count);

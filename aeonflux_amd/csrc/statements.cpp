@@ -1177,205 +1177,6 @@ extern "C" int afx_multiscalar_mul(afx_ctx* ctx, uint32_t n_terms, const uint8_t
   for (size_t i = 0; i < count; i++) ok[i] = bad[i] ? 0 : 1;
   return AFX_OK;
 } catch (...) { return afx::exception_rc(); }
-
-// ------------------------------------------------------------------------------------------------
-// wire format: header parsing on the host, AoS -> SoA transposition on the GPU
-// ------------------------------------------------------------------------------------------------
-static bool wire_shape_ok(const afx_shape& sh) {
-  if (sh.n_attributes > AFX_MAX_ATTRIBUTES || sh.n_responses > 3 + AFX_MAX_ATTRIBUTES || sh.n_hidden_scalars > AFX_MAX_ATTRIBUTES ||
-      sh.n_enc_proofs > AFX_MAX_ATTRIBUTES)
-    return false;
-  for (uint32_t i = 0; i < sh.n_attributes; i++)
-    if (sh.kinds[i] > AFX_ENC_SECRET_POINT) return false;
-  return true;
-}
-extern "C" uint32_t afx_wire_cells_per_record(const afx_shape* sh) {
-  if (!sh || !wire_shape_ok(*sh)) return 0;
-  uint32_t pub = 0;
-  for (uint32_t i = 0; i < sh->n_attributes; i++) pub += (sh->kinds[i] == AFX_ENC_PUBLIC_SCALAR || sh->kinds[i] == AFX_ENC_PUBLIC_POINT);
-  return 1 + sh->n_responses + 3 + sh->n_attributes + pub + 14 * sh->n_enc_proofs;
-}
-extern "C" size_t afx_wire_header_bytes(const afx_shape* sh) {
-  if (!sh || !wire_shape_ok(*sh)) return 0;
-  const size_t raw = 32 + sh->n_attributes + 2 * (size_t)sh->n_hidden_scalars + 2 * (size_t)sh->n_enc_proofs;
-  return (raw + 31) & ~size_t(31);
-}
-extern "C" int afx_wire_parse(const uint8_t* blob, size_t len, afx_shape* shape_out, size_t* count_out, size_t* records_offset_out) try {
-  if (!blob || !shape_out || !count_out || !records_offset_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  if (len < 32 || memcmp(blob, "AFXP", 4) != 0 || rd32(blob + 4) != 1) { set_error("not an AFXP v1 batch"); return AFX_E_BAD_ARGS; }
-  afx_shape sh;
-  memset(&sh, 0, sizeof sh);
-  const uint32_t count = rd32(blob + 8), cells = rd32(blob + 12);
-  sh.n_attributes = rd32(blob + 16); sh.n_responses = rd32(blob + 20); sh.n_hidden_scalars = rd32(blob + 24); sh.n_enc_proofs = rd32(blob + 28);
-  if (sh.n_attributes > AFX_MAX_ATTRIBUTES || sh.n_responses > 3 + AFX_MAX_ATTRIBUTES || sh.n_hidden_scalars > AFX_MAX_ATTRIBUTES || sh.n_enc_proofs > AFX_MAX_ATTRIBUTES) {
-    set_error("shape field out of range");
-    return AFX_E_BAD_ARGS;
-  }
-  const size_t raw = 32 + sh.n_attributes + 2 * (size_t)sh.n_hidden_scalars + 2 * (size_t)sh.n_enc_proofs, hdr = (raw + 31) & ~size_t(31);
-  if (len < hdr) { set_error("truncated header"); return AFX_E_BAD_ARGS; }
-  const uint8_t* p = blob + 32;
-  for (uint32_t i = 0; i < sh.n_attributes; i++) sh.kinds[i] = *p++;
-  for (uint32_t i = 0; i < sh.n_hidden_scalars; i++) { sh.hidden_scalar_indices[i] = (uint16_t)(p[0] | (p[1] << 8)); p += 2; }
-  for (uint32_t i = 0; i < sh.n_enc_proofs; i++) { sh.enc_indices[i] = (uint16_t)(p[0] | (p[1] << 8)); p += 2; }
-  if (!wire_shape_ok(sh) || cells != afx_wire_cells_per_record(&sh)) { set_error("cells_per_record does not match the shape"); return AFX_E_BAD_ARGS; }
-  if ((len - hdr) / 32 / (cells ? cells : 1) < count || len != hdr + (size_t)count * cells * 32) { set_error("record area length"); return AFX_E_BAD_ARGS; }
-  *shape_out = sh;
-  *count_out = count;
-  *records_offset_out = hdr;
-  return AFX_OK;
-} catch (...) { return afx::exception_rc(); }
-// records [first, first + n) of a parsed AFXP batch; status is the whole batch's array (element first + i answers record first + i)
-static int verify_wire_records(afx_ctx* ctx, const afx_shape& sh, const uint8_t* records, size_t count, size_t first, size_t n, uint8_t* status) {
-  if (n == 0) return AFX_OK;
-  AFX_HIP(hipSetDevice(ctx->device));
-  const uint32_t cells = afx_wire_cells_per_record(&sh);
-  // SoA rows: challenge | responses | C_x_0 C_x_1 C_V | C_y[n] | attr_values[n] (secret rows stay unused) | enc proofs
-  const uint32_t na = sh.n_attributes;
-  const uint32_t row_resp = 1, row_cx = row_resp + sh.n_responses, row_cy = row_cx + 3, row_av = row_cy + na, row_enc = row_av + na;
-  const uint32_t rows = row_enc + 14 * sh.n_enc_proofs;
-  std::vector<uint32_t> row_of_cell;
-  for (uint32_t r = 0; r < row_av; r++) row_of_cell.push_back(r);
-  for (uint32_t i = 0; i < na; i++)
-    if (sh.kinds[i] == AFX_ENC_PUBLIC_SCALAR || sh.kinds[i] == AFX_ENC_PUBLIC_POINT) row_of_cell.push_back(row_av + i);
-  for (uint32_t r = row_enc; r < rows; r++) row_of_cell.push_back(r);
-  if (row_of_cell.size() != cells) { set_error("internal: wire cell map"); return AFX_E_BAD_ARGS; }
-  // records are contiguous: a slice of the batch is a byte range of the blob; slices alternate between the two lanes like
-  // those of the column-array calls (statements.hpp host_pipe), each transposed on the GPU into its own SoA scratch
-  const afx_shape jsh = canonical_shape(sh);
-  const PlanKey jkey = plan_key("VW", &jsh, sizeof jsh, mode_flags(ctx));
-  return host_pipe(ctx, n, [&](Stager& st, size_t off, size_t sn) -> int {
-    const size_t f0 = first + off;
-    st.layout_tag = 1;
-    const size_t dn = st.dev_items(sn);
-    const size_t o_rec = st.add_rows(records, 1, (size_t)cells * 32, count, f0, sn, dn), o_map = st.add((const uint8_t*)row_of_cell.data(), 4 * (size_t)cells),
-                 o_soa = st.reserve(dn * rows * 32), o_st = st.add(nullptr, dn);
-    st.plan_fetch(status, o_st, 1, 1, count, f0, sn, dn);
-    int rc2 = st.upload();
-    if (rc2) return rc2;
-    if (!st.app) {   // (a call that took item slots of an earlier call's pass: that call's transposition covers them)
-      // the transposition reads what the upload brings: under a Session it waits for the session's one upload
-      hipStream_t strm = st.stream();
-      const uint8_t* rec_d = st.dev(o_rec);
-      uint8_t* soa_d = st.dev(o_soa);
-      const uint32_t* map_d = (const uint32_t*)st.dev(o_map);
-      const uint32_t cells_ = cells, dn_ = (uint32_t)dn;
-      auto transpose = [=]() -> int { AFX_HIP(afxk_aos_to_soa(strm, rec_d, soa_d, map_d, cells_, dn_)); return AFX_OK; };
-      if (st.ses) st.ses->pre.push_back(transpose);
-      else if ((rc2 = transpose())) return rc2;
-    }
-    auto rowp = [&](uint32_t r) { return (const uint8_t*)st.dev(o_soa) + (size_t)r * dn * 32; };
-    afx_presentation_soa d;
-    d.challenge = rowp(0);
-    d.responses = rowp(row_resp);
-    d.C_x_0 = rowp(row_cx); d.C_x_1 = rowp(row_cx + 1); d.C_V = rowp(row_cx + 2);
-    d.C_y = rowp(row_cy);
-    d.attr_values = rowp(row_av);
-    std::vector<afx_encproof_soa> encs(sh.n_enc_proofs);
-    for (uint32_t e = 0; e < sh.n_enc_proofs; e++) {
-      const uint32_t r = row_enc + 14 * e;
-      encs[e] = { rowp(r), rowp(r + 1), rowp(r + 7), rowp(r + 8), rowp(r + 9), rowp(r + 10), rowp(r + 11), rowp(r + 12), rowp(r + 13) };
-    }
-    d.enc = encs.data();
-    if ((rc2 = afx_verify_presentations_dev(ctx, &sh, &d, dn, st.dev(o_st)))) return rc2;
-    return st.fetch_all();
-  }, jkey);
-}
-extern "C" int afx_verify_presentations_wire_range(afx_ctx* ctx, const uint8_t* blob, size_t len, size_t first, size_t n, uint8_t* status, size_t status_cap,
-                                                   size_t* count_out) try {
-  CtxLock lock__(ctx, true);
-  if (!ctx || !status || !count_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  afx_shape sh;
-  size_t count = 0, off = 0;
-  int rc = afx_wire_parse(blob, len, &sh, &count, &off);
-  if (rc) return rc;
-  *count_out = count;
-  if (first > count || n > count - first) { set_error("range outside the batch"); return AFX_E_BAD_ARGS; }
-  if (n == 0) return AFX_OK;
-  if (status_cap < count) { set_error("status buffer too small"); return AFX_E_BAD_ARGS; }
-  if (count > 0xffffffffu / 64) { set_error("batch too large for one call"); return AFX_E_BAD_ARGS; }
-  if (!ctx->has_key) { set_error("Issuer::verify needs the issuer key"); return AFX_E_NO_KEY; }
-  return verify_wire_records(ctx, sh, blob + off, count, first, n, status);
-} catch (...) { return afx::exception_rc(); }
-extern "C" int afx_verify_presentations_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, uint8_t* status, size_t status_cap, size_t* count_out) try {
-  if (!count_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  size_t count = 0, hdr = 0;
-  afx_shape sh;
-  int rc = afx_wire_parse(blob, len, &sh, &count, &hdr);
-  if (rc) return rc;
-  *count_out = count;
-  return afx_verify_presentations_wire_range(ctx, blob, len, 0, count, status, status_cap, count_out);
-} catch (...) { return afx::exception_rc(); }
-
-// ---- CredentialIssuance batches ("AFXI" v1) -----------------------------------------------------
-extern "C" size_t afx_issuance_wire_header_bytes(uint32_t n_attributes) {
-  if (n_attributes > AFX_MAX_ATTRIBUTES) return 0;
-  return (24 + (size_t)n_attributes + 31) & ~size_t(31);
-}
-extern "C" int afx_issuance_wire_parse(const uint8_t* blob, size_t len, uint32_t* n_out, uint8_t kinds_out[AFX_MAX_ATTRIBUTES], uint32_t* nr_out,
-                                       size_t* count_out, size_t* records_offset_out) try {
-  if (!blob || !n_out || !kinds_out || !nr_out || !count_out || !records_offset_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  if (len < 24 || memcmp(blob, "AFXI", 4) != 0 || rd32(blob + 4) != 1) { set_error("not an AFXI v1 batch"); return AFX_E_BAD_ARGS; }
-  const uint32_t count = rd32(blob + 8), cells = rd32(blob + 12), n = rd32(blob + 16), nr = rd32(blob + 20);
-  if (n > AFX_MAX_ATTRIBUTES || nr > AFX_MAX_ATTRIBUTES + 5) { set_error("layout field out of range"); return AFX_E_BAD_ARGS; }
-  const size_t hdr = afx_issuance_wire_header_bytes(n);
-  if (len < hdr) { set_error("truncated header"); return AFX_E_BAD_ARGS; }
-  for (uint32_t i = 0; i < n; i++)
-    if (blob[24 + i] > AFX_ATTR_SECRET_POINT) { set_error("attribute kind out of range"); return AFX_E_BAD_ARGS; }
-  if (cells != 4 + nr + n) { set_error("cells_per_record does not match the layout"); return AFX_E_BAD_ARGS; }
-  if ((len - hdr) / 32 / cells < count || len != hdr + (size_t)count * cells * 32) { set_error("record area length"); return AFX_E_BAD_ARGS; }
-  memset(kinds_out, 0, AFX_MAX_ATTRIBUTES);
-  memcpy(kinds_out, blob + 24, n);
-  *n_out = n; *nr_out = nr; *count_out = count; *records_offset_out = hdr;
-  return AFX_OK;
-} catch (...) { return afx::exception_rc(); }
-extern "C" int afx_verify_issuances_wire(afx_ctx* ctx, const uint8_t* blob, size_t len, uint8_t* status, size_t status_cap, size_t* count_out) try {
-  CtxLock lock__(ctx, true);
-  if (!ctx || !status || !count_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  afx_attributes_soa at;
-  memset(&at, 0, sizeof at);
-  uint32_t nr = 0;
-  size_t count = 0, off = 0;
-  int rc = afx_issuance_wire_parse(blob, len, &at.n_attributes, at.kinds, &nr, &count, &off);
-  if (rc) return rc;
-  *count_out = count;
-  if (count == 0) return AFX_OK;
-  if (status_cap < count) { set_error("status buffer too small"); return AFX_E_BAD_ARGS; }
-  if (count > 0xffffffffu / 64) { set_error("batch too large for one call"); return AFX_E_BAD_ARGS; }
-  AFX_HIP(hipSetDevice(ctx->device));
-  const uint32_t n = at.n_attributes, cells = 4 + nr + n;
-  std::vector<uint32_t> row_of_cell(cells);
-  for (uint32_t r = 0; r < cells; r++) row_of_cell[r] = r;   // SoA rows in record order: t U V challenge responses[] values[]
-  struct { uint32_t n, nr; uint8_t kinds[AFX_MAX_ATTRIBUTES]; } jd;
-  memset(&jd, 0, sizeof jd);
-  jd.n = n; jd.nr = nr; memcpy(jd.kinds, at.kinds, AFX_MAX_ATTRIBUTES);
-  const PlanKey jkey = plan_key("VIW", &jd, sizeof jd, mode_flags(ctx));
-  return host_pipe(ctx, count, [&](Stager& st, size_t first, size_t sn) -> int {
-    st.layout_tag = 1;
-    const size_t dn = st.dev_items(sn);
-    const size_t o_rec = st.add_rows(blob + off, 1, (size_t)cells * 32, count, first, sn, dn), o_map = st.add((const uint8_t*)row_of_cell.data(), 4 * (size_t)cells),
-                 o_soa = st.reserve(dn * cells * 32), o_st = st.add(nullptr, dn);
-    st.plan_fetch(status, o_st, 1, 1, count, first, sn, dn);
-    int rc2 = st.upload();
-    if (rc2) return rc2;
-    if (!st.app) {
-      // the transposition reads what the upload brings: under a Session it waits for the session's one upload
-      hipStream_t strm = st.stream();
-      const uint8_t* rec_d = st.dev(o_rec);
-      uint8_t* soa_d = st.dev(o_soa);
-      const uint32_t* map_d = (const uint32_t*)st.dev(o_map);
-      const uint32_t cells_ = cells, dn_ = (uint32_t)dn;
-      auto transpose = [=]() -> int { AFX_HIP(afxk_aos_to_soa(strm, rec_d, soa_d, map_d, cells_, dn_)); return AFX_OK; };
-      if (st.ses) st.ses->pre.push_back(transpose);
-      else if ((rc2 = transpose())) return rc2;
-    }
-    auto rowp = [&](uint32_t r) { return (uint8_t*)st.dev(o_soa) + (size_t)r * dn * 32; };
-    afx_attributes_soa as = at;
-    as.values = rowp(4 + nr);
-    const afx_issuance_soa iss = { rowp(0), rowp(1), rowp(2), rowp(3), rowp(4) };
-    if ((rc2 = afx_verify_issuances_dev(ctx, &as, &iss, nr, dn, st.dev(o_st)))) return rc2;
-    return st.fetch_all();
-  }, jkey);
-} catch (...) { return afx::exception_rc(); }
 extern "C" int afx_ctx_issuer_parameters(afx_ctx* c, uint8_t out[64]) try {
   if (!c || !out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   CtxLock lock(c);

@@ -565,3 +565,18 @@ inline size_t host_first_slice_items(const afx_ctx* c) { return c->trace ? ~size
 // waits for the context and runs its slices itself.
 int host_pipe(afx_ctx* c, size_t count, const std::function<int(Stager&, size_t, size_t)>& slice, const PlanKey& join_key = PlanKey(),
               bool never_collect = false);
+
+// The AFXI records of one layout (n_attributes, n_responses, kinds) and where their statuses go: one section's records as they lie in
+// the caller's blob, or those of several sections of a stream, piece by piece (wire_user.cpp).  wire.cpp verify_records is the one
+// place that stages and verifies them - afx_verify_issuances_wire and afx_verify_issuances_mixed_wire both end there, under one join
+// key, so a collected call of either may take item slots of the other's pass.
+struct IssuanceRecords {
+  size_t count = 0;
+  uint32_t n = 0, nr = 0;
+  uint8_t kinds[AFX_MAX_ATTRIBUTES];
+  const uint8_t* rec = nullptr;                        // [count][4 + nr + n][32] in one piece, or null:
+  const std::vector<Stager::Piece>* pieces = nullptr;  // ... the same records section by section
+  uint8_t* status = nullptr;                           // [count]
+};
+// items [first, first + n) (internal to the library: not among its exported symbols)
+__attribute__((visibility("hidden"))) int verify_records(afx_ctx* ctx, const IssuanceRecords& B, size_t first, size_t n);

@@ -1,95 +1,41 @@
-// Batchable presentations on bytes (include/aeonflux_gpu.h "AFXB"): the header functions and the packer (host, bytes only) and the
+// Batchable presentations on bytes (include/aeonflux_gpu.h "AFXB"): the format's C functions (thin wrappers over wire_formats.hpp's
+// table) and the packer (host, bytes only) and the
 // two doors - afx_verify_presentations_batchable_wire (AFXB sections in, statuses out) and afx_show_batchable_wire (credentials in,
 // one AFXB section per group out).  Records are transposed on the GPU by the kernels the AFXP doors use (k_aos_to_soa,
-// k_soa_to_aos); the arithmetic is afx_verify_presentations_batchable_dev / afx_show_batchable_dev.  A batchable call takes the
+// k_soa_to_aos, through records.hpp); the arithmetic is afx_verify_presentations_batchable_dev / afx_show_batchable_dev.  A batchable call takes the
 // context in turn: the groups of a request run one after the other, none is collected with other threads' calls.
 #include <string.h>
 #include <map>
-#include "doors.hpp"
+#include "records.hpp"
+#include "wire_formats.hpp"
 
 namespace {
-bool shape_ok(const afx_shape& sh) {
-  if (sh.n_attributes > AFX_MAX_ATTRIBUTES || sh.n_responses > 3 + AFX_MAX_ATTRIBUTES || sh.n_hidden_scalars > AFX_MAX_ATTRIBUTES || sh.n_enc_proofs > AFX_MAX_ATTRIBUTES)
-    return false;
-  for (uint32_t i = 0; i < sh.n_attributes; i++)
-    if (sh.kinds[i] > AFX_ENC_SECRET_POINT) return false;
-  return true;
-}
-bool revealed(uint8_t kind) { return kind == AFX_ENC_PUBLIC_SCALAR || kind == AFX_ENC_PUBLIC_POINT; }
-// a main proof has the commitments of the reference's statement or of the strict one: nothing else is a well-formed header
-bool n_main_ok(const afx_shape& sh, uint32_t n_main) { return n_main == afx_batchable_n_main_of(sh, false) || n_main == afx_batchable_n_main_of(sh, true); }
-void write_header(uint8_t* h, size_t hdr, const afx_shape& sh, uint32_t n_main, uint32_t cells, size_t count) {
-  memset(h, 0, hdr);
-  memcpy(h, "AFXB", 4);
-  wr32(h + 4, 1); wr32(h + 8, (uint32_t)count); wr32(h + 12, cells);
-  wr32(h + 16, sh.n_attributes); wr32(h + 20, sh.n_responses); wr32(h + 24, sh.n_hidden_scalars); wr32(h + 28, sh.n_enc_proofs); wr32(h + 32, n_main);
-  uint8_t* p = h + 36;
-  for (uint32_t i = 0; i < sh.n_attributes; i++) *p++ = sh.kinds[i];
-  for (uint32_t i = 0; i < sh.n_hidden_scalars; i++) { *p++ = (uint8_t)sh.hidden_scalar_indices[i]; *p++ = (uint8_t)(sh.hidden_scalar_indices[i] >> 8); }
-  for (uint32_t i = 0; i < sh.n_enc_proofs; i++) { *p++ = (uint8_t)sh.enc_indices[i]; *p++ = (uint8_t)(sh.enc_indices[i] >> 8); }
-}
 // Rows of the struct-of-arrays scratch both doors use, in record order but for the revealed values:
 //   R[n_main] | responses[nr] | C_x_0 C_x_1 C_V | C_y[na] | per proof of encryption: R[5] responses[6] pk E1 E2 C_y_1 C_y_2 C_y_3 C_y_2p
 struct Rows {
   uint32_t resp, cx, cy, enc, end;
   Rows(const afx_shape& sh, uint32_t n_main) : resp(n_main), cx(resp + sh.n_responses), cy(cx + 3), enc(cy + sh.n_attributes), end(enc + 18 * sh.n_enc_proofs) {}
 };
-// cell -> row: the rows above, a revealed value's cell at values_row + its attribute position
-std::vector<uint32_t> cell_map(const afx_shape& sh, const Rows& R, uint32_t values_row) {
-  std::vector<uint32_t> m;
-  for (uint32_t r = 0; r < R.enc; r++) m.push_back(r);
-  for (uint32_t i = 0; i < sh.n_attributes; i++)
-    if (revealed(sh.kinds[i])) m.push_back(values_row + i);
-  for (uint32_t r = R.enc; r < R.end; r++) m.push_back(r);
-  return m;
-}
 }  // namespace
 
+// ---- the AFXB format (wire_formats.hpp): host only, bytes only ----
 extern "C" size_t afx_batchable_wire_header_bytes(const afx_shape* sh) {
-  if (!sh || !shape_ok(*sh)) return 0;
-  return (36 + sh->n_attributes + 2 * (size_t)sh->n_hidden_scalars + 2 * (size_t)sh->n_enc_proofs + 31) & ~size_t(31);
+  return sh && shape_ok(*sh) ? header_bytes(FORMATS[AFXB], sh->n_attributes, sh->n_hidden_scalars, sh->n_enc_proofs) : 0;
 }
 extern "C" uint32_t afx_batchable_wire_cells_per_record(const afx_shape* sh, uint32_t n_main_commitments) {
-  if (!sh || !shape_ok(*sh) || !n_main_ok(*sh, n_main_commitments)) return 0;
-  uint32_t pub = 0;
-  for (uint32_t i = 0; i < sh->n_attributes; i++) pub += revealed(sh->kinds[i]);
-  return n_main_commitments + sh->n_responses + 3 + sh->n_attributes + pub + 18 * sh->n_enc_proofs;
+  return sh && shape_ok(*sh) && n_main_ok(*sh, n_main_commitments) ? presentation_cells(*sh, n_main_commitments, 18) : 0;
 }
 extern "C" int afx_batchable_wire_parse(const uint8_t* blob, size_t len, afx_shape* shape_out, uint32_t* n_main_out, size_t* count_out, size_t* records_offset_out) try {
   if (!blob || !shape_out || !n_main_out || !count_out || !records_offset_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  if (len < 36 || memcmp(blob, "AFXB", 4) != 0 || rd32(blob + 4) != 1) { set_error("not an AFXB v1 batch"); return AFX_E_BAD_ARGS; }
-  afx_shape sh;
-  memset(&sh, 0, sizeof sh);
-  const uint32_t count = rd32(blob + 8), cells = rd32(blob + 12), n_main = rd32(blob + 32);
-  sh.n_attributes = rd32(blob + 16); sh.n_responses = rd32(blob + 20); sh.n_hidden_scalars = rd32(blob + 24); sh.n_enc_proofs = rd32(blob + 28);
-  if (sh.n_attributes > AFX_MAX_ATTRIBUTES || sh.n_responses > 3 + AFX_MAX_ATTRIBUTES || sh.n_hidden_scalars > AFX_MAX_ATTRIBUTES || sh.n_enc_proofs > AFX_MAX_ATTRIBUTES) {
-    set_error("shape field out of range");
-    return AFX_E_BAD_ARGS;
-  }
-  const size_t hdr = (36 + sh.n_attributes + 2 * (size_t)sh.n_hidden_scalars + 2 * (size_t)sh.n_enc_proofs + 31) & ~size_t(31);
-  if (len < hdr) { set_error("truncated header"); return AFX_E_BAD_ARGS; }
-  const uint8_t* p = blob + 36;
-  for (uint32_t i = 0; i < sh.n_attributes; i++) sh.kinds[i] = *p++;
-  for (uint32_t i = 0; i < sh.n_hidden_scalars; i++) { sh.hidden_scalar_indices[i] = (uint16_t)(p[0] | (p[1] << 8)); p += 2; }
-  for (uint32_t i = 0; i < sh.n_enc_proofs; i++) { sh.enc_indices[i] = (uint16_t)(p[0] | (p[1] << 8)); p += 2; }
-  if (!shape_ok(sh)) { set_error("attribute kind out of range"); return AFX_E_BAD_ARGS; }
-  if (!n_main_ok(sh, n_main)) { set_error("n_main_commitments does not match the shape"); return AFX_E_BAD_ARGS; }
-  if (cells != afx_batchable_wire_cells_per_record(&sh, n_main)) { set_error("cells_per_record does not match the shape"); return AFX_E_BAD_ARGS; }
-  if ((len - hdr) / 32 / cells < count || len != hdr + (size_t)count * cells * 32) { set_error("record area length"); return AFX_E_BAD_ARGS; }
-  *shape_out = sh; *n_main_out = n_main; *count_out = count; *records_offset_out = hdr;
+  Header H;
+  const int rc = read_header(FORMATS[AFXB], blob, len, H);
+  if (rc) return rc;
+  *shape_out = shape_of(H); *n_main_out = H.n_main; *count_out = H.count; *records_offset_out = H.hdr;
   return AFX_OK;
 } catch (...) { return afx::exception_rc(); }
 // the length of the section that starts at blob (its header names it); the section itself is checked by afx_batchable_wire_parse
 extern "C" int afx_batchable_wire_section_bytes(const uint8_t* blob, size_t len, size_t* section_len_out) try {
-  if (!blob || !section_len_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  if (len < 36 || memcmp(blob, "AFXB", 4) != 0 || rd32(blob + 4) != 1) { set_error("not an AFXB v1 batch"); return AFX_E_BAD_ARGS; }
-  const uint32_t count = rd32(blob + 8), cells = rd32(blob + 12), na = rd32(blob + 16), hs = rd32(blob + 24), ne = rd32(blob + 28);
-  if (na > AFX_MAX_ATTRIBUTES || hs > AFX_MAX_ATTRIBUTES || ne > AFX_MAX_ATTRIBUTES || cells == 0 || cells > 4096) { set_error("shape field out of range"); return AFX_E_BAD_ARGS; }
-  const size_t hdr = (36 + na + 2 * (size_t)hs + 2 * (size_t)ne + 31) & ~size_t(31);
-  const size_t sl = hdr + (size_t)count * cells * 32;
-  if (sl > len) { set_error("truncated section"); return AFX_E_BAD_ARGS; }
-  *section_len_out = sl;
-  return AFX_OK;
+  return section_bytes(FORMATS[AFXB], blob, len, section_len_out);
 } catch (...) { return afx::exception_rc(); }
 
 extern "C" int afx_batchable_wire_pack(const afx_shape* shape, const afx_presentation_soa* batch, const afx_commitments_soa* cm, uint32_t n_main, size_t count,
@@ -112,7 +58,7 @@ extern "C" int afx_batchable_wire_pack(const afx_shape* shape, const afx_present
     missing |= !cm->enc[e] || !q.responses || !q.pk || !q.E1 || !q.E2 || !q.C_y_1 || !q.C_y_2 || !q.C_y_3 || !q.C_y_2p;
   }
   if (missing) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
-  write_header(blob, hdr, sh, n_main, cells, count);
+  write_header(FORMATS[AFXB], blob, sh, count, cells, n_main);
   std::vector<const uint8_t*> col;
   auto rows = [&](const uint8_t* base, uint32_t k) { for (uint32_t r = 0; r < k; r++) col.push_back(base + (size_t)r * count * 32); };
   rows(cm->main, n_main); rows(b.responses, sh.n_responses); rows(b.C_x_0, 1); rows(b.C_x_1, 1); rows(b.C_V, 1); rows(b.C_y, sh.n_attributes);
@@ -147,7 +93,7 @@ int verify_group(afx_ctx* ctx, const VGroup& G, const afx_device_rng& rng, uint8
   const afx_shape& sh = G.sh;
   const Rows R(sh, G.n_main);
   const uint32_t values_row = R.end, rows = values_row + sh.n_attributes;
-  const std::vector<uint32_t> map = cell_map(sh, R, values_row);
+  const std::vector<uint32_t> map = presentation_map(sh, R.resp, 18, values_row, R.enc);
   if (map.size() != G.cells) { set_error("internal: AFXB cell map"); return AFX_E_BAD_ARGS; }
   const size_t n = G.total;
   std::vector<Stager::Piece> pieces;
@@ -158,7 +104,7 @@ int verify_group(afx_ctx* ctx, const VGroup& G, const afx_device_rng& rng, uint8
                o_soa = st.reserve(n * rows * 32), o_st = st.add(nullptr, n);
   int rc = st.upload();
   if (rc) return rc;
-  AFX_HIP(afxk_aos_to_soa(st.stream(), st.dev(o_rec), st.dev(o_soa), (const uint32_t*)st.dev(o_map), G.cells, (uint32_t)n));
+  if ((rc = transpose_in(st, o_rec, o_soa, o_map, G.cells, n))) return rc;   // (a Stager of the call's own: at once)
   auto rowp = [&](uint32_t r) { return st.dev(o_soa) + (size_t)r * n * 32; };
   std::vector<afx_encproof_soa> encs(sh.n_enc_proofs);
   std::vector<uint8_t*> cenc(sh.n_enc_proofs);
@@ -188,12 +134,12 @@ extern "C" int afx_verify_presentations_batchable_wire(afx_ctx* ctx, const uint8
   std::map<std::string, size_t> by_shape;
   size_t off = 0, total = 0;
   while (off < len) {
-    size_t sl = 0, cnt = 0, rec = 0;
-    afx_shape sh;
-    uint32_t n_main = 0;
-    int rc = afx_batchable_wire_section_bytes(blob + off, len - off, &sl);
-    if (!rc) rc = afx_batchable_wire_parse(blob + off, sl, &sh, &n_main, &cnt, &rec);
+    Header H;
+    const int rc = read_section(FORMATS[AFXB], blob + off, len - off, H);
     if (rc) { set_error("section at byte " + std::to_string(off) + ": " + afx_last_error()); return rc; }
+    const afx_shape sh = shape_of(H);
+    const uint32_t n_main = H.n_main;
+    const size_t sl = H.section, cnt = H.count, rec = H.hdr;
     const uint32_t expect = afx_batchable_main_commitments(ctx, &sh);
     if (expect && expect != n_main) { set_error("section at byte " + std::to_string(off) + ": n_main_commitments is not what this context verifies for the shape"); return AFX_E_BAD_ARGS; }
     const afx_shape csh = canonical_shape(sh);
@@ -270,7 +216,7 @@ int show_group(afx_ctx* ctx, const afx_show_group& G, const BJob& J, uint8_t* re
   const bool kp = G.keypairs && nsp;
   const Rows R(sh, J.n_main);
   const uint32_t chal = R.end, values_row = (chal + 1 + nsp + 7) & ~7u;   // the compact challenges (written, not sent), then pad: values_row * n * 32 is a multiple of 256
-  const std::vector<uint32_t> map = cell_map(sh, R, values_row);
+  const std::vector<uint32_t> map = presentation_map(sh, R.resp, 18, values_row, R.enc);
   if (map.size() != J.cells) { set_error("internal: AFXB show cell map"); return AFX_E_BAD_ARGS; }
   Stager st(ctx);
   auto in = [&](const uint8_t* p, size_t k, size_t elem) { return st.add(p, k * n * elem); };
@@ -301,7 +247,7 @@ int show_group(afx_ctx* ctx, const afx_show_group& G, const BJob& J, uint8_t* re
   const afx_commitments_soa dcm = { rowp(0), ce.data() };
   afx_shape shape_dev;
   if ((rc = afx_show_batchable_dev(ctx, &dc, kp ? &dk : nullptr, &dr, n, &dout, &dcm, &shape_dev, st.dev(o_st)))) return rc;
-  AFX_HIP(afxk_soa_to_aos(st.stream(), soa_d, st.dev(o_out), (const uint32_t*)st.dev(o_map), st.dev(o_st), J.cells, (uint32_t)n));
+  if ((rc = transpose_out(st, o_soa, o_out, o_map, o_st, J.cells, n))) return rc;   // (a Stager of the call's own: at once)
   AFX_HIP(hipMemcpyAsync(rec_out, st.dev(o_out), n * J.cells * 32, hipMemcpyDeviceToHost, st.stream()));
   AFX_HIP(hipMemcpyAsync(status, st.dev(o_st), n, hipMemcpyDeviceToHost, st.stream()));
   AFX_HIP(hipStreamSynchronize(st.stream()));
@@ -364,7 +310,7 @@ extern "C" int afx_show_batchable_wire(afx_ctx* ctx, afx_show_group* groups, siz
     const BJob& J = jobs[g];
     const size_t count = G.count;
     uint8_t* h = out + J.out_off;
-    write_header(h, J.hdr, J.sh, J.n_main, J.cells, count);
+    write_header(FORMATS[AFXB], h, J.sh, count, J.cells, J.n_main);
     std::vector<uint8_t> st_buf(count, AFX_ST_VERIFICATION_FAILURE);
     if (J.no_key) {   // CredentialError::NoSymmetricKey, as afx_show answers it: zero records
       memset(h + J.hdr, 0, count * J.cells * 32);

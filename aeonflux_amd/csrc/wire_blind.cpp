@@ -1,6 +1,7 @@
 // The issuer's side of blind issuance on bytes (include/aeonflux_gpu.h "Blind issuance on bytes"): AFXQ request sections in, AFXJ
 // issuance sections out, and the request's verification alone over the same sections.  The doors are request_stream.hpp's, as
-// wire_issue.cpp's are (this file says what an AFXQ door is: blind_door, and what it stages and launches: run_records): the records of
+// wire_issue.cpp's are; the two headers are entries of wire_formats.hpp's table, whose C functions stand here; the transpositions and
+// their cell maps are records.hpp's (this file says what an AFXQ door is: blind_door, and what it stages and launches: run_records): the records of
 // one layout are transposed to struct-of-arrays rows on the GPU (k_aos_to_soa), afx_issue_blind_dev runs on those rows and writes its
 // outputs into further rows of the same region, and k_soa_to_aos turns those into AFXJ records - zeros for an item that failed - which
 // come back in one fetch.  Only bytes move on the host.  The explicit form takes its four draws per request from host arrays, the
@@ -9,46 +10,10 @@
 // collector of other threads' calls: blind issuance plans are not laid out for shared item slots.
 #include <string>
 #include <vector>
-#include "kernels.h"
+#include "records.hpp"
 #include "request_stream.hpp"
 
 namespace {
-
-// what each format adds: the response count and the cell count that go with the kinds
-int check_request_header(const uint8_t* blob, const Header& H) {
-  const Hidden hd = hidden_of(blob + 24, H.n);
-  if (H.nr != 1 + hd.h + hd.hs) { set_error("n_responses does not match the kinds"); return AFX_E_BAD_ARGS; }
-  if (H.cells != 3 + 2 * hd.h + hd.hs + H.n) { set_error("cells_per_record does not match the layout"); return AFX_E_BAD_ARGS; }
-  return AFX_OK;
-}
-int check_issuance_header(const Header& H) {
-  if (H.nr > AFX_MAX_ATTRIBUTES + 6) { set_error("n_responses out of range"); return AFX_E_BAD_ARGS; }
-  if (H.cells != 5 + H.nr) { set_error("cells_per_record does not match the layout"); return AFX_E_BAD_ARGS; }
-  return AFX_OK;
-}
-int parse_section(const uint8_t* blob, size_t len, bool request, uint32_t* n_out, uint8_t* kinds_out, uint32_t* nr_out, size_t* count_out, size_t* rec_out) {
-  if (!blob || !n_out || !kinds_out || !nr_out || !count_out || !rec_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  Header H;
-  int rc = read_header(blob, len, request ? "AFXQ" : "AFXJ", H);
-  if (!rc) rc = request ? check_request_header(blob, H) : check_issuance_header(H);
-  if (rc) return rc;
-  if (len - H.hdr != (size_t)H.count * H.cells * 32) { set_error("record area length"); return AFX_E_BAD_ARGS; }   // (count * cells * 32 < 2^45)
-  memset(kinds_out, 0, AFX_MAX_ATTRIBUTES);
-  memcpy(kinds_out, blob + 24, H.n);
-  *n_out = H.n; *nr_out = H.nr; *count_out = H.count; *rec_out = H.hdr;
-  return AFX_OK;
-}
-int section_bytes(const uint8_t* blob, size_t len, bool request, size_t* section_len_out) {
-  if (!blob || !section_len_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  Header H;
-  int rc = read_header(blob, len, request ? "AFXQ" : "AFXJ", H);
-  if (!rc) rc = request ? check_request_header(blob, H) : check_issuance_header(H);
-  if (rc) return rc;
-  const uint64_t total = (uint64_t)H.hdr + (uint64_t)H.count * H.cells * 32;   // (< 2^46)
-  if (total > len) { set_error("section runs past the end of the blob"); return AFX_E_BAD_ARGS; }
-  *section_len_out = (size_t)total;
-  return AFX_OK;
-}
 
 // Items [first, first + n) of a batch.  Per pass, one region of scratch holds the rows
 //   D | A[h] | B[h] | challenge | responses[1 + h + hs] | values[n] | t | U | S1 | S2 | challenge | responses[n + 6]
@@ -64,11 +29,10 @@ int run_records(afx_ctx* ctx, const Batch& B, size_t first, size_t n) {
   if (issue && !ctx->has_key) { set_error("blind issuance needs the issuer key"); return AFX_E_NO_KEY; }
   if (B.n != ctx->n) { set_error("internal: request layout of another context"); return AFX_E_BAD_ARGS; }
   const uint32_t na = B.n, h = B.h, rq = 3 + 3 * h + B.hs, cells_in = B.cells_in, out_cells = issue ? na + 11 : 0, rows = rq + na + out_cells;
-  std::vector<uint32_t> map_in(cells_in), map_out(out_cells ? out_cells : 1);
-  for (uint32_t c = 0; c < rq; c++) map_in[c] = c;   // D, A, B, challenge, responses: the record's order is the rows' order
-  for (uint32_t i = 0, c = rq; i < na; i++)
-    if (!is_hidden_kind(B.kinds[i])) map_in[c++] = rq + i;   // a revealed value lands on the row of its position
-  for (uint32_t c = 0; c < out_cells; c++) map_out[c] = rq + na + c;
+  // D, A, B, challenge, responses: the record's order is the rows' order; a revealed value lands on the row of its position
+  const std::vector<uint32_t> map_in = blind_request_map(B.kinds, na, rq, 0, rq);
+  const std::vector<uint32_t> map_out = issue ? identity_map(out_cells, rq + na) : std::vector<uint32_t>(1);   // (the verification alone stages one unused word)
+  if (map_in.size() != cells_in) { set_error("internal: AFXQ cell map"); return AFX_E_BAD_ARGS; }
   const size_t total = B.count;
   return host_pipe(ctx, n, [&](Stager& st, size_t off, size_t sn) -> int {
     if (st.ses || st.app) { set_error("internal: a blind wire call inside a collected session"); return AFX_E_BAD_ARGS; }
@@ -96,9 +60,8 @@ int run_records(afx_ctx* ctx, const Batch& B, size_t first, size_t n) {
     st.plan_fetch(B.status, o_st, 1, 1, total, f0, sn, dn);
     int rc = st.upload();
     if (rc) return rc;
-    hipStream_t strm = st.stream();
     uint8_t* soa_d = st.dev(o_soa);
-    AFX_HIP(afxk_aos_to_soa(strm, st.dev(o_rec), soa_d, (const uint32_t*)st.dev(o_min), cells_in, (uint32_t)dn));
+    if ((rc = transpose_in(st, o_rec, o_soa, o_min, cells_in, dn))) return rc;   // (never in a session: at once)
     auto rowp = [&](uint32_t r) { return soa_d + (size_t)r * dn * 32; };
     afx_attributes_soa da;
     memset(&da, 0, sizeof da);
@@ -113,23 +76,18 @@ int run_records(afx_ctx* ctx, const Batch& B, size_t first, size_t n) {
     const afx_blind_issue_randomness dr = { st.dev(o_tw), st.dev(o_uw), st.dev(o_rw), st.dev(o_seed) };
     const afx_blind_issuance_soa dout = { rowp(o0), rowp(o0 + 1), rowp(o0 + 2), rowp(o0 + 3), rowp(o0 + 4), rowp(o0 + 5) };
     if ((rc = afx_issue_blind_dev(ctx, &da, &dq, B.nrq, &dr, dn, &dout, st.dev(o_st)))) return rc;
-    AFX_HIP(afxk_soa_to_aos(strm, soa_d, st.dev(o_out), (const uint32_t*)st.dev(o_mout), st.dev(o_st), out_cells, (uint32_t)dn));
+    if ((rc = transpose_out(st, o_soa, o_out, o_mout, o_st, out_cells, dn))) return rc;
     return st.fetch_all();
   }, PlanKey(), true);   // never collected: a small call too runs its slices itself
 }
 
-int parse_request(const uint8_t* blob, size_t len, uint32_t* n_out, uint8_t* kinds_out, uint32_t* nrq_out, size_t* count_out, size_t* rec_out) {
-  return parse_section(blob, len, true, n_out, kinds_out, nrq_out, count_out, rec_out);
-}
 // The AFXQ door (request_stream.hpp): a request record is D | A[h] | B[h] | challenge | responses[1 + h + hs] | the revealed values, an
 // AFXJ record is t | U | S1 | S2 | challenge | responses[ctx n + 6], and a request takes t_wide, U_wide, rprime_wide and rng_seed.
 // rnd == null: every column null (the _rng form, and the verification alone).  issue == false: afx_verify_blind_requests_wire.
 // Several batches run one after another: run_records never hands a call to the collector.
 Door blind_door(const afx_blind_issue_randomness* rnd, bool issue) {
   Door d = {};
-  d.out_magic = "AFXJ";
-  d.section_bytes = [](const uint8_t* blob, size_t len, size_t* out) { return section_bytes(blob, len, true, out); };
-  d.parse = parse_request;
+  d.in = &FORMATS[AFXQ]; d.out = &FORMATS[AFXJ];
   d.cells_in = [](uint32_t n, uint32_t h, uint32_t hs) { return 3 + 2 * h + hs + n; };
   d.cells_out = [](uint32_t, uint32_t ctx_n) { return ctx_n + 11; };
   d.n_responses = [](uint32_t ctx_n) { return ctx_n + 6; };
@@ -148,30 +106,30 @@ Door blind_door(const afx_blind_issue_randomness* rnd, bool issue) {
 }  // namespace
 
 // ---- the two formats: host only, bytes only ----
-extern "C" size_t afx_blind_request_wire_header_bytes(uint32_t n_attributes) { return header_bytes(n_attributes); }
-extern "C" size_t afx_blind_issuance_wire_header_bytes(uint32_t n_attributes) { return header_bytes(n_attributes); }
+extern "C" size_t afx_blind_request_wire_header_bytes(uint32_t n_attributes) { return header_bytes(FORMATS[AFXQ], n_attributes); }
+extern "C" size_t afx_blind_issuance_wire_header_bytes(uint32_t n_attributes) { return header_bytes(FORMATS[AFXJ], n_attributes); }
 
 extern "C" int afx_blind_request_wire_parse(const uint8_t* blob, size_t len, uint32_t* n_attributes_out, uint8_t kinds_out[AFX_MAX_ATTRIBUTES],
                                             uint32_t* n_responses_out, size_t* count_out, size_t* records_offset_out) try {
-  return parse_section(blob, len, true, n_attributes_out, kinds_out, n_responses_out, count_out, records_offset_out);
+  return parse_layout(FORMATS[AFXQ], blob, len, n_attributes_out, kinds_out, n_responses_out, count_out, records_offset_out);
 } catch (...) { return afx::exception_rc(); }
 extern "C" int afx_blind_issuance_wire_parse(const uint8_t* blob, size_t len, uint32_t* n_attributes_out, uint8_t kinds_out[AFX_MAX_ATTRIBUTES],
                                              uint32_t* n_responses_out, size_t* count_out, size_t* records_offset_out) try {
-  return parse_section(blob, len, false, n_attributes_out, kinds_out, n_responses_out, count_out, records_offset_out);
+  return parse_layout(FORMATS[AFXJ], blob, len, n_attributes_out, kinds_out, n_responses_out, count_out, records_offset_out);
 } catch (...) { return afx::exception_rc(); }
 
 extern "C" int afx_blind_request_wire_section_bytes(const uint8_t* blob, size_t len, size_t* section_len_out) try {
-  return section_bytes(blob, len, true, section_len_out);
+  return section_bytes(FORMATS[AFXQ], blob, len, section_len_out);
 } catch (...) { return afx::exception_rc(); }
 extern "C" int afx_blind_issuance_wire_section_bytes(const uint8_t* blob, size_t len, size_t* section_len_out) try {
-  return section_bytes(blob, len, false, section_len_out);
+  return section_bytes(FORMATS[AFXJ], blob, len, section_len_out);
 } catch (...) { return afx::exception_rc(); }
 
 extern "C" int afx_blind_request_wire_pack(const afx_attributes_soa* attrs, const afx_blind_request_soa* requests, size_t count, uint8_t* blob, size_t blob_cap,
                                            size_t* len_out) try {
   if (!attrs || !requests || !len_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   const uint32_t n = attrs->n_attributes;
-  const size_t hdr = header_bytes(n);
+  const size_t hdr = header_bytes(FORMATS[AFXQ], n);
   if (hdr == 0 || count > 0xffffffffu) { set_error("layout out of range"); return AFX_E_BAD_ARGS; }
   for (uint32_t i = 0; i < n; i++)
     if (attrs->kinds[i] > AFX_ATTR_SECRET_POINT) { set_error("attribute kind out of range"); return AFX_E_BAD_ARGS; }
@@ -183,7 +141,7 @@ extern "C" int afx_blind_request_wire_pack(const afx_attributes_soa* attrs, cons
   if (blob_cap < len) { set_error("blob buffer too small"); return AFX_E_BAD_ARGS; }
   const afx_blind_request_soa& q = *requests;
   if (count && (!q.D || !q.challenge || !q.responses || (h && (!q.A || !q.B)) || (n > h && !attrs->values))) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
-  write_header(blob, "AFXQ", hdr, count, cells, n, nr, attrs->kinds);
+  write_header(FORMATS[AFXQ], blob, count, cells, n, nr, attrs->kinds);
   uint8_t* rec = blob + hdr;
   auto put = [&](const uint8_t* base, size_t row, size_t i) { memcpy(rec, base + (row * count + i) * 32, 32); rec += 32; };
   for (size_t i = 0; i < count; i++) {
@@ -202,7 +160,7 @@ extern "C" int afx_blind_issuance_wire_pack(const afx_attributes_soa* attrs, con
                                             uint8_t* blob, size_t blob_cap, size_t* len_out) try {
   if (!attrs || !issuances || !len_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   const uint32_t n = attrs->n_attributes;
-  const size_t hdr = header_bytes(n);
+  const size_t hdr = header_bytes(FORMATS[AFXJ], n);
   if (hdr == 0 || count > 0xffffffffu || n_responses > AFX_MAX_ATTRIBUTES + 6) { set_error("layout out of range"); return AFX_E_BAD_ARGS; }
   for (uint32_t i = 0; i < n; i++)
     if (attrs->kinds[i] > AFX_ATTR_SECRET_POINT) { set_error("attribute kind out of range"); return AFX_E_BAD_ARGS; }
@@ -213,7 +171,7 @@ extern "C" int afx_blind_issuance_wire_pack(const afx_attributes_soa* attrs, con
   if (blob_cap < len) { set_error("blob buffer too small"); return AFX_E_BAD_ARGS; }
   const afx_blind_issuance_soa& s = *issuances;
   if (count && (!s.t || !s.U || !s.S1 || !s.S2 || !s.challenge || (n_responses && !s.responses))) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
-  write_header(blob, "AFXJ", hdr, count, cells, n, n_responses, attrs->kinds);
+  write_header(FORMATS[AFXJ], blob, count, cells, n, n_responses, attrs->kinds);
   uint8_t* rec = blob + hdr;
   auto put = [&](const uint8_t* base, size_t row, size_t i) { memcpy(rec, base + (row * count + i) * 32, 32); rec += 32; };
   for (size_t i = 0; i < count; i++) {

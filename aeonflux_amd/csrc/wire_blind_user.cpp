@@ -6,11 +6,12 @@
 // rows and k_soa_to_aos make the records of them; the unblinding door transposes both record streams into one row region
 // (k_aos_to_soa), runs afx_unblind_issuances_dev on it and copies t, U and V out through k_soa_to_aos, which zeroes a failed item.
 // Like wire_blind.cpp's doors a call takes the context in turn and stages slice after slice on the two lanes (host_pipe); it is never
-// handed to the collector of other threads' calls.  The formats' parsers are wire_blind.cpp's.
+// handed to the collector of other threads' calls.  The two formats are entries of wire_formats.hpp's table; the cell maps are records.hpp's
+// (the launches here stay where they are: they interleave with k_reduce_wide and the wipes).
 #include <map>
 #include <string>
 #include <vector>
-#include "kernels.h"
+#include "records.hpp"
 #include "request_stream.hpp"
 
 namespace {
@@ -88,7 +89,7 @@ int plan_request(uint32_t ctx_n, const afx_blind_request_group* groups, size_t n
     if (G.count > 0xffffffffu / 64) { set_error("too many requests in one group"); return AFX_E_BAD_ARGS; }
     G.first = P.total;
     G.out_off = P.out_len;
-    G.hdr = header_bytes(G.n);
+    G.hdr = header_bytes(FORMATS[AFXQ], G.n);
     const size_t bytes = G.hdr + G.count * G.cells * 32;   // (< 2^26 * 2^8 * 2^5)
     if (__builtin_add_overflow(P.out_len, bytes, &P.out_len) || __builtin_add_overflow(P.total, G.count, &P.total)) {
       set_error("request stream too large");
@@ -111,11 +112,10 @@ int run_request(afx_ctx* ctx, const ReqGroup& G, size_t first, size_t n) {
   AFX_HIP(hipSetDevice(ctx->device));
   if (G.n != ctx->n) { set_error("internal: request layout of another context"); return AFX_E_BAD_ARGS; }
   const uint32_t na = G.n, h = G.h, rq = 3 + 3 * h + G.hs, cells = G.cells;
-  std::vector<uint32_t> map(cells);
+  // D, A, B, challenge, responses: the rows' order is the record's; the value rows lie in front of them
+  const std::vector<uint32_t> map = blind_request_map(G.kinds, na, rq, na, 0);
+  if (map.size() != cells) { set_error("internal: AFXQ cell map"); return AFX_E_BAD_ARGS; }
   const uint32_t one_cell = 0;
-  for (uint32_t c = 0; c < rq; c++) map[c] = na + c;   // D, A, B, challenge, responses: the rows' order is the record's
-  for (uint32_t i = 0, c = rq; i < na; i++)
-    if (!is_hidden_kind(G.kinds[i])) map[c++] = i;
   const afx_blind_request_group& g = *G.g;
   const size_t total = G.count;
   const std::vector<Stager::DrawPiece> draws = { { 0, total, (uint64_t)G.first } };
@@ -194,7 +194,7 @@ int request_wire(const Where& w, const afx_blind_request_group* groups, size_t n
   std::vector<size_t> counts;
   for (ReqGroup& G : P.groups) {
     uint8_t* hd = out + G.out_off;
-    write_header(hd, "AFXQ", G.hdr, G.count, G.cells, G.n, G.nr, G.kinds);
+    write_header(FORMATS[AFXQ], hd, G.count, G.cells, G.n, G.nr, G.kinds);
     G.rec = hd + G.hdr;
     G.status = status + G.first;
     G.d_out = d_out ? d_out + G.first * 32 : nullptr;
@@ -256,19 +256,16 @@ int parse_pairs(const uint8_t* iss, size_t iss_len, const uint8_t* req, size_t r
   while (jo < iss_len || qo < req_len) {
     const std::string at = "section " + std::to_string(S.pairs.size()) + ": ";
     if (jo >= iss_len || qo >= req_len) { set_error("the issuance stream and the request stream differ in their section counts"); return AFX_E_BAD_ARGS; }
-    size_t jl = 0, ql = 0, jc = 0, qc = 0, jr = 0, qr = 0;
-    uint32_t jn = 0, qn = 0, jnr = 0, qnr = 0;
-    uint8_t jk[AFX_MAX_ATTRIBUTES], qk[AFX_MAX_ATTRIBUTES];
-    int rc = afx_blind_issuance_wire_section_bytes(iss + jo, iss_len - jo, &jl);
-    if (!rc) rc = afx_blind_issuance_wire_parse(iss + jo, jl, &jn, jk, &jnr, &jc, &jr);
+    Header J, Q;
+    int rc = read_section(FORMATS[AFXJ], iss + jo, iss_len - jo, J);
     if (rc) { set_error(at + "issuance: " + afx_last_error()); return rc; }
-    rc = afx_blind_request_wire_section_bytes(req + qo, req_len - qo, &ql);
-    if (!rc) rc = afx_blind_request_wire_parse(req + qo, ql, &qn, qk, &qnr, &qc, &qr);
-    if (rc) { set_error(at + "request: " + afx_last_error()); return rc; }
-    if (jc != qc || jn != qn || memcmp(jk, qk, AFX_MAX_ATTRIBUTES) != 0) { set_error(at + "the issuance section does not answer the request section (count, n_attributes or kinds)"); return AFX_E_BAD_ARGS; }
+    if ((rc = read_section(FORMATS[AFXQ], req + qo, req_len - qo, Q))) { set_error(at + "request: " + afx_last_error()); return rc; }
+    if (J.count != Q.count || J.n != Q.n || memcmp(J.kinds, Q.kinds, J.n) != 0) { set_error(at + "the issuance section does not answer the request section (count, n_attributes or kinds)"); return AFX_E_BAD_ARGS; }
+    const size_t jc = J.count, jl = J.section, ql = Q.section;
     Pair p;
-    p.q_rec = qo + qr; p.j_rec = jo + jr; p.count = jc; p.first = S.total; p.n = jn; p.nrj = jnr;
-    memcpy(p.kinds, jk, AFX_MAX_ATTRIBUTES);
+    p.q_rec = qo + Q.hdr; p.j_rec = jo + J.hdr; p.count = jc; p.first = S.total; p.n = J.n; p.nrj = J.nr;
+    memset(p.kinds, 0, sizeof p.kinds);
+    memcpy(p.kinds, J.kinds, J.n);
     if (__builtin_add_overflow(S.total, jc, &S.total)) { set_error("issuance stream too large"); return AFX_E_BAD_ARGS; }
     if (on_gpu(p, ctx_n) && jc) {
       const std::string key((const char*)p.kinds, p.n);
@@ -305,11 +302,9 @@ int run_unblind(afx_ctx* ctx, const UBatch& B, size_t first, size_t n) {
   const uint32_t na = B.n, h = B.h, rq = 3 + 3 * h + B.hs, j0 = rq + na, v_row = j0 + na + 11, d_row = v_row + 1;
   const bool drawn = B.seed40 != nullptr;
   const uint32_t rows = d_row + (drawn ? 1 : 0);
-  std::vector<uint32_t> map_q(B.cells_q), map_j(B.cells_j);
-  for (uint32_t c = 0; c < rq; c++) map_q[c] = c;
-  for (uint32_t i = 0, c = rq; i < na; i++)
-    if (!is_hidden_kind(B.kinds[i])) map_q[c++] = rq + i;   // a revealed value lands on the row of its position
-  for (uint32_t c = 0; c < B.cells_j; c++) map_j[c] = j0 + c;
+  // (a revealed value lands on the row of its position)
+  const std::vector<uint32_t> map_q = blind_request_map(B.kinds, na, rq, 0, rq), map_j = identity_map(B.cells_j, j0);
+  if (map_q.size() != B.cells_q) { set_error("internal: AFXQ cell map"); return AFX_E_BAD_ARGS; }
   const uint32_t map_o[3] = { j0, j0 + 1, v_row };
   const size_t total = B.count;
   return host_pipe(ctx, n, [&](Stager& st, size_t off, size_t sn) -> int {

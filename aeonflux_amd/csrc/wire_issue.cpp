@@ -4,26 +4,21 @@
 // afx_issue_dev writes its outputs into the rows in front of the attribute values, and k_soa_to_aos turns the whole region back into
 // AFXI records - zeros for an item that failed - which come back in one fetch.  Only bytes move on the host.
 // Splitting the stream, merging its sections by layout, the answers' headers and the group form are request_stream.hpp's, shared with
-// wire_blind.cpp; this file says what an AFXR door is (request_door) and what it stages and launches (issue_records).
+// wire_blind.cpp; the AFXR header is an entry of wire_formats.hpp's table and the two transpositions are records.hpp's.  This file says
+// what an AFXR door is (request_door) and what it stages and launches (issue_records), and holds the format's C functions.
 #include <string>
 #include <vector>
-#include "kernels.h"
+#include "records.hpp"
 #include "request_stream.hpp"
 
 namespace {
 
 int issue_records(afx_ctx* ctx, const Batch& B, size_t first, size_t n);
-int parse_request(const uint8_t* blob, size_t len, uint32_t* n_out, uint8_t* kinds_out, uint32_t* nrq_out, size_t* count_out, size_t* rec_out) {
-  *nrq_out = 0;   // (an AFXR request carries no proof)
-  return afx_request_wire_parse(blob, len, n_out, kinds_out, count_out, rec_out);
-}
 // The AFXR door (request_stream.hpp): a request record holds the attribute values only, an AFXI record is t | U | V | challenge |
 // responses[ctx n + 5] | values[n], and a request takes t_wide, U_wide and rng_seed.  rnd == null: every column null (the _rng forms).
 Door request_door(const afx_issue_randomness* rnd) {
   Door d = {};
-  d.out_magic = "AFXI";
-  d.section_bytes = afx_request_wire_section_bytes;
-  d.parse = parse_request;
+  d.in = &FORMATS[AFXR]; d.out = &FORMATS[AFXI];   // (an AFXR request carries no proof: its sections' nrq is 0)
   d.cells_in = [](uint32_t n, uint32_t, uint32_t) { return n; };
   d.cells_out = [](uint32_t n, uint32_t ctx_n) { return 4 + (ctx_n + 5) + n; };
   d.n_responses = [](uint32_t ctx_n) { return ctx_n + 5; };
@@ -48,9 +43,8 @@ int issue_records(afx_ctx* ctx, const Batch& B, size_t first, size_t n) {
   if (!ctx->has_key) { set_error("Issuer::issue needs the issuer key"); return AFX_E_NO_KEY; }
   if (B.n != ctx->n) { set_error("internal: request layout of another context"); return AFX_E_BAD_ARGS; }
   const uint32_t na = B.n, nr = ctx->n + 5, cells = 4 + nr + na;
-  std::vector<uint32_t> map_in(na), map_out(cells);
-  for (uint32_t c = 0; c < na; c++) map_in[c] = 4 + nr + c;   // a request record holds the values only
-  for (uint32_t c = 0; c < cells; c++) map_out[c] = c;         // an AFXI record is the region's rows in order
+  // a request record holds the values only; an AFXI record is the region's rows in order
+  const std::vector<uint32_t> map_in = identity_map(na, 4 + nr), map_out = identity_map(cells);
   struct { uint32_t n; uint8_t kinds[AFX_MAX_ATTRIBUTES]; } jd;   // what makes two calls one pass (statements.hpp host_pipe)
   memset(&jd, 0, sizeof jd);
   jd.n = na; memcpy(jd.kinds, B.kinds, AFX_MAX_ATTRIBUTES);
@@ -78,17 +72,8 @@ int issue_records(afx_ctx* ctx, const Batch& B, size_t first, size_t n) {
     st.plan_fetch(B.status, o_st, 1, 1, total, f0, sn, dn);
     int rc = st.upload();
     if (rc) return rc;
-    // (a call that took item slots of an earlier call's pass: that call's two transpositions cover them)
-    hipStream_t strm = st.stream();
+    if ((rc = transpose_in(st, o_rec, o_soa, o_min, na, dn))) return rc;
     uint8_t* soa_d = st.dev(o_soa);
-    const uint32_t dn_ = (uint32_t)dn;
-    if (!st.app) {
-      const uint8_t* rec_d = st.dev(o_rec);
-      const uint32_t* map_d = (const uint32_t*)st.dev(o_min);
-      auto transpose = [=]() -> int { AFX_HIP(afxk_aos_to_soa(strm, rec_d, soa_d, map_d, na, dn_)); return AFX_OK; };
-      if (st.ses) st.ses->pre.push_back(transpose);
-      else if ((rc = transpose())) return rc;
-    }
     auto rowp = [&](uint32_t r) { return soa_d + (size_t)r * dn * 32; };
     afx_attributes_soa da;
     memset(&da, 0, sizeof da);
@@ -97,53 +82,23 @@ int issue_records(afx_ctx* ctx, const Batch& B, size_t first, size_t n) {
     const afx_issue_randomness dr = { st.dev(o_tw), st.dev(o_uw), st.dev(o_seed) };
     const afx_issuance_soa dout = { rowp(0), rowp(1), rowp(2), rowp(3), rowp(4) };
     if ((rc = afx_issue_dev(ctx, &da, &dr, dn, &dout, st.dev(o_st)))) return rc;
-    if (!st.app) {
-      uint8_t* out_d = st.dev(o_out);
-      const uint32_t* map_d = (const uint32_t*)st.dev(o_mout);
-      const uint8_t* st_d = st.dev(o_st);
-      auto transpose = [=]() -> int { AFX_HIP(afxk_soa_to_aos(strm, soa_d, out_d, map_d, st_d, cells, dn_)); return AFX_OK; };
-      if (st.ses) st.ses->post.push_back(transpose);
-      else if ((rc = transpose())) return rc;
-    }
+    if ((rc = transpose_out(st, o_soa, o_out, o_mout, o_st, cells, dn))) return rc;
     return st.fetch_all();
   }, jkey);
 }
 
 }  // namespace
 
-extern "C" size_t afx_request_wire_header_bytes(uint32_t n_attributes) {
-  if (n_attributes > AFX_MAX_ATTRIBUTES) return 0;
-  return (20 + (size_t)n_attributes + 31) & ~size_t(31);
-}
+// ---- the AFXR format (wire_formats.hpp): host only, bytes only ----
+extern "C" size_t afx_request_wire_header_bytes(uint32_t n_attributes) { return header_bytes(FORMATS[AFXR], n_attributes); }
 
 extern "C" int afx_request_wire_parse(const uint8_t* blob, size_t len, uint32_t* n_out, uint8_t kinds_out[AFX_MAX_ATTRIBUTES], size_t* count_out,
                                       size_t* records_offset_out) try {
-  if (!blob || !n_out || !kinds_out || !count_out || !records_offset_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  if (len < 20 || memcmp(blob, "AFXR", 4) != 0 || rd32(blob + 4) != 1) { set_error("not an AFXR v1 batch"); return AFX_E_BAD_ARGS; }
-  const uint32_t count = rd32(blob + 8), cells = rd32(blob + 12), n = rd32(blob + 16);
-  if (n > AFX_MAX_ATTRIBUTES) { set_error("n_attributes out of range"); return AFX_E_BAD_ARGS; }
-  const size_t hdr = afx_request_wire_header_bytes(n);
-  if (len < hdr) { set_error("truncated header"); return AFX_E_BAD_ARGS; }
-  for (uint32_t i = 0; i < n; i++)
-    if (blob[20 + i] > AFX_ATTR_SECRET_POINT) { set_error("attribute kind out of range"); return AFX_E_BAD_ARGS; }
-  if (cells != n) { set_error("cells_per_record does not match the layout"); return AFX_E_BAD_ARGS; }
-  if (len - hdr != (size_t)count * n * 32) { set_error("record area length"); return AFX_E_BAD_ARGS; }   // (count * n * 32 < 2^42)
-  memset(kinds_out, 0, AFX_MAX_ATTRIBUTES);
-  memcpy(kinds_out, blob + 20, n);
-  *n_out = n; *count_out = count; *records_offset_out = hdr;
-  return AFX_OK;
+  uint32_t no_responses;
+  return parse_layout(FORMATS[AFXR], blob, len, n_out, kinds_out, &no_responses, count_out, records_offset_out);
 } catch (...) { return afx::exception_rc(); }
-
 extern "C" int afx_request_wire_section_bytes(const uint8_t* blob, size_t len, size_t* section_len_out) try {
-  if (!blob || !section_len_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  if (len < 20 || memcmp(blob, "AFXR", 4) != 0 || rd32(blob + 4) != 1) { set_error("not an AFXR v1 section"); return AFX_E_BAD_ARGS; }
-  const uint64_t count = rd32(blob + 8), cells = rd32(blob + 12);
-  const uint32_t n = rd32(blob + 16);
-  if (n > AFX_MAX_ATTRIBUTES || cells != n) { set_error("layout field out of range"); return AFX_E_BAD_ARGS; }
-  const uint64_t total = (uint64_t)afx_request_wire_header_bytes(n) + count * cells * 32;   // (< 2^42)
-  if (total > len) { set_error("section runs past the end of the blob"); return AFX_E_BAD_ARGS; }
-  *section_len_out = (size_t)total;
-  return AFX_OK;
+  return section_bytes(FORMATS[AFXR], blob, len, section_len_out);
 } catch (...) { return afx::exception_rc(); }
 
 extern "C" int afx_request_wire_pack(const afx_attributes_soa* requests, size_t count, uint8_t* blob, size_t blob_cap, size_t* len_out) try {
@@ -158,10 +113,7 @@ extern "C" int afx_request_wire_pack(const afx_attributes_soa* requests, size_t 
   if (count && n && !requests->values) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
   for (uint32_t i = 0; i < n; i++)
     if (requests->kinds[i] > AFX_ATTR_SECRET_POINT) { set_error("attribute kind out of range"); return AFX_E_BAD_ARGS; }
-  memset(blob, 0, hdr);
-  memcpy(blob, "AFXR", 4);
-  wr32(blob + 4, 1); wr32(blob + 8, (uint32_t)count); wr32(blob + 12, n); wr32(blob + 16, n);
-  memcpy(blob + 20, requests->kinds, n);
+  write_header(FORMATS[AFXR], blob, count, n, n, 0, requests->kinds);
   uint8_t* rec = blob + hdr;
   for (size_t i = 0; i < count; i++)
     for (uint32_t c = 0; c < n; c++, rec += 32) memcpy(rec, requests->values + ((size_t)c * count + i) * 32, 32);

@@ -1,7 +1,8 @@
 // The user side of the protocol on bytes (include/aeonflux_gpu.h afx_verify_issuances_mixed_wire, afx_show_wire).
 //  - CredentialIssuance::verify (the crate's src/issuer.rs:48-57) over a stream of AFXI sections, as afx_issue_wire writes them:
 //    sections of one layout are merged wherever they stand (and staged from where they lie), the records are transposed to
-//    struct-of-arrays on the GPU (k_aos_to_soa) and verified as afx_verify_issuances_wire verifies one section.
+//    struct-of-arrays on the GPU and verified by the function that verifies afx_verify_issuances_wire's one section (wire.cpp
+//    verify_records; the AFXI format's C functions stand there too).
 //  - AnonymousCredential::show (src/credential.rs:37-46) straight into AFXP sections: afx_show_dev writes its outputs into the rows of
 //    one scratch region per pass, the revealed attribute values are read from the credential's own value rows, and k_soa_to_aos turns
 //    the region into AFXP records - zeros for an item that failed - which come back in one fetch.
@@ -10,8 +11,8 @@
 #include <map>
 #include <string>
 #include <vector>
-#include "kernels.h"
-#include "doors.hpp"
+#include "records.hpp"
+#include "wire_formats.hpp"
 
 namespace {
 
@@ -25,14 +26,10 @@ struct ISection {
 // The issuances of one (n_attributes, n_responses, kinds), merged over the sections that carry it: their records stay where they lie
 // in the caller's blob (staged piece by piece); the statuses go to the caller's array when ONE section carries the layout, else to a
 // buffer of the batch's own, scattered afterwards.
-struct IBatch {
+struct IBatch : IssuanceRecords {      // (statements.hpp: the layout, where the records lie, where the statuses go)
   std::vector<size_t> secs;
-  size_t count = 0;
-  uint32_t n = 0, nr = 0;
-  uint8_t kinds[AFX_MAX_ATTRIBUTES];
+  std::vector<Stager::Piece> in_pieces;   // the records of several sections, where they lie in the caller's blob
   bool fails = false;                  // a layout every item fails on (afx_verify_issuances_dev's fail_all): answered here
-  std::vector<Stager::Piece> pieces;   // the records [count][4 + nr + n][32], section by section
-  uint8_t* status = nullptr;           // [count]
   std::vector<uint8_t> st_buf;
 };
 struct IStream {
@@ -47,12 +44,15 @@ int parse_issuances(const uint8_t* blob, size_t len, uint32_t ctx_n, IStream& S)
   if (!blob && len) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   std::map<std::string, size_t> by_layout;
   for (size_t off = 0; off < len;) {
-    size_t sl = 0, cnt = 0, rec = 0;
-    ISection s;
-    int rc = afx_issuance_wire_section_bytes(blob + off, len - off, &sl);
-    if (!rc) rc = afx_issuance_wire_parse(blob + off, sl, &s.n, s.kinds, &s.nr, &cnt, &rec);
+    Header H;
+    const int rc = read_section(FORMATS[AFXI], blob + off, len - off, H);
     if (rc) { set_error("section at byte " + std::to_string(off) + ": " + afx_last_error()); return rc; }
-    s.off = off; s.hdr = rec; s.count = cnt; s.first = S.total;
+    const size_t cnt = H.count;
+    ISection s;
+    s.off = off; s.hdr = H.hdr; s.count = cnt; s.first = S.total;
+    s.n = H.n; s.nr = H.nr;
+    memset(s.kinds, 0, sizeof s.kinds);
+    memcpy(s.kinds, H.kinds, H.n);
     S.total += cnt;   // (< len / 32)
     if (cnt) {
       std::string key((const char*)&s.nr, sizeof s.nr);
@@ -72,7 +72,7 @@ int parse_issuances(const uint8_t* blob, size_t len, uint32_t ctx_n, IStream& S)
       S.batches[it->second].count += cnt;
     }
     S.secs.push_back(s);
-    off += sl;
+    off += H.section;
   }
   return AFX_OK;
 }
@@ -94,11 +94,15 @@ void prepare_issuances(IStream& S, const uint8_t* blob, uint8_t* status) {
     size_t at = 0;
     for (size_t k : B.secs) {
       const ISection& s = S.secs[k];
-      B.pieces.push_back({ at, s.count, blob + s.off + s.hdr });
+      B.in_pieces.push_back({ at, s.count, blob + s.off + s.hdr });
       at += s.count;
     }
-    if (B.secs.size() == 1) B.status = status + S.secs[B.secs[0]].first;
-    else { B.st_buf.assign(B.count, AFX_ST_VERIFICATION_FAILURE); B.status = B.st_buf.data(); }
+    if (B.secs.size() == 1) { B.rec = B.in_pieces[0].src; B.status = status + S.secs[B.secs[0]].first; }
+    else {   // (the batch points into itself: S.batches neither grows nor moves from here on)
+      B.pieces = &B.in_pieces;
+      B.st_buf.assign(B.count, AFX_ST_VERIFICATION_FAILURE);
+      B.status = B.st_buf.data();
+    }
   }
 }
 void scatter_issuances(const IStream& S, uint8_t* status) {
@@ -111,53 +115,6 @@ void scatter_issuances(const IStream& S, uint8_t* status) {
       at += s.count;
     }
   }
-}
-
-// Items [first, first + n) of a batch, staged exactly as afx_verify_issuances_wire stages one section (statements.cpp), under the same
-// join key: a collected call of either front end may take item slots of the other's pass.
-int verify_records(afx_ctx* ctx, const IBatch& B, size_t first, size_t n) {
-  CtxLock lock__(ctx, true);
-  if (n == 0) return AFX_OK;
-  AFX_HIP(hipSetDevice(ctx->device));
-  const uint32_t na = B.n, nr = B.nr, cells = 4 + nr + na;
-  std::vector<uint32_t> row_of_cell(cells);
-  for (uint32_t r = 0; r < cells; r++) row_of_cell[r] = r;   // SoA rows in record order: t U V challenge responses[] values[]
-  struct { uint32_t n, nr; uint8_t kinds[AFX_MAX_ATTRIBUTES]; } jd;
-  memset(&jd, 0, sizeof jd);
-  jd.n = na; jd.nr = nr; memcpy(jd.kinds, B.kinds, AFX_MAX_ATTRIBUTES);
-  const PlanKey jkey = plan_key("VIW", &jd, sizeof jd, mode_flags(ctx));
-  const size_t total = B.count;
-  return host_pipe(ctx, n, [&](Stager& st, size_t off, size_t sn) -> int {
-    const size_t f0 = first + off;
-    st.layout_tag = 1;
-    const size_t dn = st.dev_items(sn);
-    // (one section: its records as afx_verify_issuances_wire stages them; several: the same region, filled section by section)
-    const size_t o_rec = B.pieces.size() == 1 ? st.add_rows(B.pieces[0].src, 1, (size_t)cells * 32, total, f0, sn, dn)
-                                              : st.add_rows_pieces(B.pieces, (size_t)cells * 32, total, f0, sn, dn),
-                 o_map = st.add((const uint8_t*)row_of_cell.data(), 4 * (size_t)cells),
-                 o_soa = st.reserve(dn * cells * 32), o_st = st.add(nullptr, dn);
-    st.plan_fetch(B.status, o_st, 1, 1, total, f0, sn, dn);
-    int rc = st.upload();
-    if (rc) return rc;
-    if (!st.app) {   // (a call that took item slots of an earlier call's pass: that call's transposition covers them)
-      hipStream_t strm = st.stream();
-      const uint8_t* rec_d = st.dev(o_rec);
-      uint8_t* soa_d = st.dev(o_soa);
-      const uint32_t* map_d = (const uint32_t*)st.dev(o_map);
-      const uint32_t dn_ = (uint32_t)dn;
-      auto transpose = [=]() -> int { AFX_HIP(afxk_aos_to_soa(strm, rec_d, soa_d, map_d, cells, dn_)); return AFX_OK; };
-      if (st.ses) st.ses->pre.push_back(transpose);
-      else if ((rc = transpose())) return rc;
-    }
-    auto rowp = [&](uint32_t r) { return st.dev(o_soa) + (size_t)r * dn * 32; };
-    afx_attributes_soa as;
-    memset(&as, 0, sizeof as);
-    as.n_attributes = na; memcpy(as.kinds, B.kinds, AFX_MAX_ATTRIBUTES);
-    as.values = rowp(4 + nr);
-    const afx_issuance_soa iss = { rowp(0), rowp(1), rowp(2), rowp(3), rowp(4) };
-    if ((rc = afx_verify_issuances_dev(ctx, &as, &iss, nr, dn, st.dev(o_st)))) return rc;
-    return st.fetch_all();
-  }, jkey);
 }
 
 std::vector<size_t> launch_counts(const IStream& S) {
@@ -263,14 +220,7 @@ void prepare_show(SPlan& P, uint8_t* out, uint8_t* status) {
     const afx_shape& sh = J.sh;
     const size_t count = J.g->count;
     uint8_t* h = out + J.out_off;
-    memset(h, 0, J.hdr);
-    memcpy(h, "AFXP", 4);
-    wr32(h + 4, 1); wr32(h + 8, (uint32_t)count); wr32(h + 12, J.cells);
-    wr32(h + 16, sh.n_attributes); wr32(h + 20, sh.n_responses); wr32(h + 24, sh.n_hidden_scalars); wr32(h + 28, sh.n_enc_proofs);
-    uint8_t* p = h + 32;
-    for (uint32_t i = 0; i < sh.n_attributes; i++) *p++ = sh.kinds[i];
-    for (uint32_t i = 0; i < sh.n_hidden_scalars; i++) { *p++ = (uint8_t)sh.hidden_scalar_indices[i]; *p++ = (uint8_t)(sh.hidden_scalar_indices[i] >> 8); }
-    for (uint32_t i = 0; i < sh.n_enc_proofs; i++) { *p++ = (uint8_t)sh.enc_indices[i]; *p++ = (uint8_t)(sh.enc_indices[i] >> 8); }
+    write_header(FORMATS[AFXP], h, sh, count, J.cells);
     J.rec = h + J.hdr;
     if (J.g->positions) { J.st_buf.assign(count, AFX_ST_VERIFICATION_FAILURE); J.status = J.st_buf.data(); }
     else J.status = status + next;
@@ -309,11 +259,7 @@ int show_records(afx_ctx* ctx, const SJob& J, size_t first, size_t n, const uint
   const uint32_t na = sh.n_attributes, nr = sh.n_responses, nsp = sh.n_enc_proofs, cells = J.cells;
   const bool kp = G.keypairs && nsp;
   const uint32_t r_x = 1 + nr, r_cy = r_x + 3, r_enc = r_cy + na, rows = r_enc + 14 * nsp, r_val = (rows + 7) & ~7u;   // (r_val * dn * 32: a multiple of 256)
-  std::vector<uint32_t> map;
-  for (uint32_t r = 0; r < r_enc; r++) map.push_back(r);
-  for (uint32_t i = 0; i < na; i++)
-    if (sh.kinds[i] == AFX_ENC_PUBLIC_SCALAR || sh.kinds[i] == AFX_ENC_PUBLIC_POINT) map.push_back(r_val + i);
-  for (uint32_t r = r_enc; r < rows; r++) map.push_back(r);
+  const std::vector<uint32_t> map = presentation_map(sh, 1, 14, r_val, r_enc);
   if (map.size() != cells) { set_error("internal: show wire cell map"); return AFX_E_BAD_ARGS; }
   struct { uint32_t n; uint8_t kinds[AFX_MAX_ATTRIBUTES]; } jd;   // what makes two calls one pass (statements.hpp host_pipe)
   memset(&jd, 0, sizeof jd);
@@ -361,35 +307,11 @@ int show_records(afx_ctx* ctx, const SJob& J, size_t first, size_t n, const uint
     const afx_presentation_out dout = { rowp(0), rowp(1), rowp(r_x), rowp(r_x + 1), rowp(r_x + 2), rowp(r_cy), nullptr, nsp ? de.data() : nullptr };
     afx_shape shape_dev;
     if ((rc = afx_show_dev(ctx, &dc, kp ? &dk : nullptr, &dr, dn, &dout, &shape_dev, st.dev(o_st)))) return rc;
-    if (!st.app) {   // (a call that took item slots of an earlier call's pass: that call's transposition covers them)
-      hipStream_t strm = st.stream();
-      uint8_t* out_d = st.dev(o_out);
-      const uint32_t* map_d = (const uint32_t*)st.dev(o_map);
-      const uint8_t* st_d = st.dev(o_st);
-      const uint32_t dn_ = (uint32_t)dn;
-      auto transpose = [=]() -> int { AFX_HIP(afxk_soa_to_aos(strm, soa_d, out_d, map_d, st_d, cells, dn_)); return AFX_OK; };
-      if (st.ses) st.ses->post.push_back(transpose);
-      else if ((rc = transpose())) return rc;
-    }
+    if ((rc = transpose_out(st, o_soa, o_out, o_map, o_st, cells, dn))) return rc;
     return st.fetch_all();
   }, jkey);
 }
 
-}  // namespace
-
-extern "C" int afx_issuance_wire_section_bytes(const uint8_t* blob, size_t len, size_t* section_len_out) try {
-  if (!blob || !section_len_out) { set_error("null argument"); return AFX_E_BAD_ARGS; }
-  if (len < 24 || memcmp(blob, "AFXI", 4) != 0 || rd32(blob + 4) != 1) { set_error("not an AFXI v1 section"); return AFX_E_BAD_ARGS; }
-  const uint64_t count = rd32(blob + 8), cells = rd32(blob + 12);
-  const uint32_t n = rd32(blob + 16), nr = rd32(blob + 20);
-  if (n > AFX_MAX_ATTRIBUTES || nr > AFX_MAX_ATTRIBUTES + 5 || cells != 4 + (uint64_t)nr + n) { set_error("layout field out of range"); return AFX_E_BAD_ARGS; }
-  const uint64_t total = (uint64_t)afx_issuance_wire_header_bytes(n) + count * cells * 32;   // (< 2^32 * 2^7 * 2^5)
-  if (total > len) { set_error("section runs past the end of the blob"); return AFX_E_BAD_ARGS; }
-  *section_len_out = (size_t)total;
-  return AFX_OK;
-} catch (...) { return afx::exception_rc(); }
-
-namespace {
 // a parsed stream (parse_issuances with this context's n) on one context
 int verify_stream(afx_ctx* ctx, IStream& S, const uint8_t* blob, uint8_t* status, size_t status_cap) {
   int rc = check_issuances(S, status, status_cap);

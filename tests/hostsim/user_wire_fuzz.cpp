@@ -7,6 +7,8 @@
 // mutated stream goes through the section measure and the stream verification in EXACT-size heap buffers (an over-read of one byte
 // lands in a red zone), with a status buffer of the reported size and one byte short; then afx_show_wire gets size queries of every
 // layout, full calls and damaged positions.  Every call must return AFX_OK or AFX_E_BAD_ARGS.
+// Before any of that, on a context of its own: afx_verify_issuances_wire and afx_verify_issuances_mixed_wire stage one section alike -
+// the plan the first call assembles serves the second call and the stream's (shared_plan_cache).
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -158,6 +160,44 @@ static void show_cases(unsigned long long target, unsigned long long& m) {
   }
 }
 
+// One 3-item AFXI section of 2 attributes (n_responses = the context's n + 5: a layout the stream verifies on the device) through
+// afx_verify_issuances_wire twice, then through afx_verify_issuances_mixed_wire: the second and the third call take the first call's
+// plans from the cache - hits and not one miss - because both entry points stage the section in one function (wire.cpp verify_records).
+static void shared_plan_cache(const Bytes& params, const Bytes& ip) {
+  afx_ctx* c = nullptr;
+  if (afx_ctx_create(&c, 0, params.data(), params.size(), nullptr, 0, ip.data())) { fprintf(stderr, "ctx: %s\n", afx_last_error()); exit(2); }
+  afx_ctx_set_coalescing(c, 0, 0);
+  const size_t count = 3;
+  const uint32_t n = 2, nr = afx_ctx_n_attributes(c) + 5;
+  afx_attributes_soa at;
+  memset(&at, 0, sizeof at);
+  at.n_attributes = n; at.kinds[0] = AFX_ATTR_PUBLIC_SCALAR; at.kinds[1] = AFX_ATTR_PUBLIC_POINT;
+  Bytes values(n * count * 32), t(count * 32), U(count * 32), V(count * 32), ch(count * 32), resp(nr * count * 32);
+  for (Bytes* b : { &values, &t, &U, &V, &ch, &resp }) for (uint8_t& x : *b) x = (uint8_t)rnd();
+  at.values = values.data();
+  const afx_issuance_soa iss = { t.data(), U.data(), V.data(), ch.data(), resp.data() };
+  size_t len = 0;
+  if (afx_issuance_wire_pack(&at, &iss, nr, count, nullptr, 0, &len)) { fprintf(stderr, "pack: %s\n", afx_last_error()); exit(1); }
+  Bytes blob(len);
+  if (afx_issuance_wire_pack(&at, &iss, nr, count, blob.data(), blob.size(), &len)) { fprintf(stderr, "pack: %s\n", afx_last_error()); exit(1); }
+  afx_plan_cache_stats s[4];
+  uint8_t st[3];
+  size_t cnt = 0;
+  afx_ctx_get_plan_cache_stats(c, &s[0]);
+  for (int k = 1; k <= 3; k++) {
+    const int rc = k < 3 ? afx_verify_issuances_wire(c, blob.data(), blob.size(), st, sizeof st, &cnt) : afx_verify_issuances_mixed_wire(c, blob.data(), blob.size(), st, sizeof st, &cnt);
+    if (rc || cnt != count) { fprintf(stderr, "shared plan cache: call %d returned %d (%s), %zu items\n", k, rc, afx_last_error(), cnt); exit(1); }
+    afx_ctx_get_plan_cache_stats(c, &s[k]);
+  }
+  fprintf(stderr, "shared plan cache: hits %llu %llu %llu %llu, misses %llu %llu %llu %llu\n", (unsigned long long)s[0].hits, (unsigned long long)s[1].hits,
+          (unsigned long long)s[2].hits, (unsigned long long)s[3].hits, (unsigned long long)s[0].misses, (unsigned long long)s[1].misses,
+          (unsigned long long)s[2].misses, (unsigned long long)s[3].misses);
+  if (s[1].misses <= s[0].misses) { fprintf(stderr, "shared plan cache: the first call assembled nothing\n"); exit(1); }
+  for (int k = 2; k <= 3; k++)
+    if (s[k].hits <= s[k - 1].hits || s[k].misses != s[k - 1].misses) { fprintf(stderr, "shared plan cache: call %d did not run on the first call's plans\n", k); exit(1); }
+  afx_ctx_destroy(c);
+}
+
 int main(int argc, char** argv) {
   if (argc < 3) return 2;
   const std::string dir = argv[1];
@@ -165,6 +205,7 @@ int main(int argc, char** argv) {
   const Bytes params = rd(dir + "/params.bin"), ip = rd(dir + "/ip.bin");
   if (afx_ctx_create(&ctx, 0, params.data(), params.size(), nullptr, 0, ip.data())) { fprintf(stderr, "ctx: %s\n", afx_last_error()); return 2; }
   afx_ctx_set_coalescing(ctx, 0, 0);   // (one thread: nothing to collect)
+  shared_plan_cache(params, ip);
   const Bytes A = rd(dir + "/a.afxi"), B = rd(dir + "/b.afxi"), M3 = rd(dir + "/m.afxi"), Z = rd(dir + "/z.afxi"), X = rd(dir + "/mixed.afxi");
   const std::vector<Bytes> seeds = { A, B, M3, Z, X };
   for (const Bytes& g : seeds) hit(g);

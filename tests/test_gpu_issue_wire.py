@@ -4,6 +4,8 @@ streams come back in request order with failed records zeroed; large streams run
 many threads are collected into shared passes; a group of devices gives the one-context bytes."""
 import ctypes as C
 import functools
+import hashlib
+import struct
 import threading
 
 import numpy as np
@@ -68,6 +70,37 @@ def test_issue_wire_is_the_oracles_afxi_and_the_column_path(n, layout, count, mo
     want, st2 = issue_then_pack(ctx, w["kinds"], w["values"], w["rnd"])
     assert st2.tolist() == [0] * count and got == want
     ctx.close()
+
+
+@pytest.mark.parametrize("count", [1, 63, 65])
+@pytest.mark.parametrize("n,layout", [(1, "P"), (3, "SSP")])
+def test_issue_wire_rng_then_the_stream_verification_are_the_column_calls(n, layout, count):
+    """Below, at and above a wave, on padded passes (16, 64 and 128 items), with 1 and 3 attributes: afx_issue_wire_rng gives the statuses and
+    the bytes of afx_issue on the same draws (SHAKE256, include/aeonflux_gpu.h afx_device_rng) packed as AFXI, and
+    afx_verify_issuances_mixed_wire the statuses of afx_verify_issuances on the same records - as issued, and with the last one damaged."""
+    import aeonflux_amd as afx
+    from aeonflux_amd import batch, wire
+    w = world(n, layout, 65)
+    d, kinds, values = w["d"], w["kinds"], np.ascontiguousarray(w["values"][:, :count])
+    seed, stream = bytes(range(32)), 5
+    draw = lambda label, size: np.frombuffer(b"".join(hashlib.shake_256(b"aeonflux-amd/device-rng/v1" + seed + struct.pack("<QQB", stream, i, label)).digest(size)
+                                                      for i in range(count)), np.uint8).reshape(count, size)
+    issuer = afx.Context(d["params"], d["key"], d["ip"])
+    got, status = wire.issue_wire_rng(issuer, wire.pack_requests(kinds, values), seed=seed, stream=stream)
+    o, st_col = batch.issue(issuer, kinds, values, draw(0, 64), draw(1, 64), draw(2, 32))
+    issuer.close()
+    assert status.tolist() == st_col.tolist() == [0] * count
+    assert got == wire.pack_issuances(kinds, values, o)
+    cells = 4 + (n + 5) + n
+    rec = records(got, 32, cells).copy()
+    rec[count - 1, 2 * 32 + 3] ^= 1   # V of the last item
+    o_bad = {k: v.copy() for k, v in o.items()}
+    o_bad["V"][count - 1, 3] ^= 1
+    user = afx.Context(d["params"], None, d["ip"])
+    for blob, cols, want in ((got, o, [0] * count), (got[:32] + rec.tobytes(), o_bad, [0] * (count - 1) + [1])):
+        st_wire = wire.verify_issuances_stream(user, blob).tolist()
+        assert st_wire == batch.verify_issuances(user, kinds, values, cols).tolist() == want
+    user.close()
 
 
 def test_response_verifies_on_the_user_side_and_a_tampered_record_gets_the_oracles_verdict():

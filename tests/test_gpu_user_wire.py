@@ -470,3 +470,26 @@ def test_group_gives_the_one_context_bytes():
     for w, x in zip(wver, gver):
         assert x.tolist() == w.tolist()
     assert wver[1][5:5 + count].tolist() == [0] * count
+
+
+def test_one_section_and_the_stream_share_the_plan_cache():
+    """afx_verify_issuances_wire and afx_verify_issuances_mixed_wire stage a section in one function (wire.cpp verify_records): on a fresh
+    context the first call of a 3-item section of 2 attributes assembles the plans, the same call again and then the stream's entry point
+    on the same bytes run on them - hits, and not one miss more (tests/hostsim/user_wire_fuzz.cpp shared_plan_cache is the host's half)."""
+    from aeonflux_amd import wire
+    d = world("SSPE", 12)
+    rng = np.random.default_rng(31)
+    iss = {k: rng.integers(0, 256, size=(3, 32), dtype=np.uint8) for k in ("t", "U", "V", "challenge")}
+    iss["responses"] = rng.integers(0, 256, size=(N + 5, 3, 32), dtype=np.uint8)
+    blob = wire.pack_issuances([0, 2], rng.integers(0, 256, size=(2, 3, 32), dtype=np.uint8), iss)
+    user = user_ctx(d)
+    s = [user.plan_cache_stats()]
+    got = []
+    for call in (user.verify_issuances_wire, user.verify_issuances_wire, lambda b: wire.verify_issuances_stream(user, b)):
+        got.append(call(blob)[:3].tolist())
+        s.append(user.plan_cache_stats())
+    user.close()
+    assert got[0] == got[1] == got[2] and 0 not in got[0]   # (random bytes verify nowhere)
+    assert s[1]["misses"] > s[0]["misses"]
+    for k in (2, 3):
+        assert s[k]["hits"] > s[k - 1]["hits"] and s[k]["misses"] == s[k - 1]["misses"], s

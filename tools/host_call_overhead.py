@@ -1,10 +1,13 @@
 """Host share of a small call, on a CPU: the engine's host half of a tree built plain against the fake HIP runtime (tests/hostsim, the
 source list of tests/test_launch_kinds_host.py), where a call is almost purely assemble / reuse, relocate and run_plans.
     python tools/host_call_overhead.py [--tree DIR] [--rounds 5] [--calls 2000]
-times `--calls` verify_presentations calls of 1 item and of 16 items on the C3 fixture, end to end, in a fresh process per round;
-with --tree (a checkout of another commit: tools/ab_trees.sh says how to make one) the two trees alternate.  Prints us per call."""
+times `--calls` verify_presentations calls of 1 item and of 16 items on the C3 fixture, end to end, and as many calls of their serialized
+twin - afx_verify_presentations_wire on the same presentations packed as one AFXP batch - in a fresh process per round; with --tree (a
+checkout of another commit: tools/ab_trees.sh says how to make one) the two trees alternate.  Prints us per call and, at the end, every
+tree's median and its spread (max - min) over the rounds."""
 import argparse
 import os
+import statistics
 import subprocess
 import sys
 import tempfile
@@ -20,12 +23,12 @@ import numpy as np
 import aeonflux_amd as afx
 afx.LIB_PATH = %(lib)r
 import bench
-from aeonflux_amd import batch
+from aeonflux_amd import batch, wire
 p3, k3, i3 = bench.load_fixture("c3_8attrs_SSPPeeee")
 ctx = afx.Context(p3, k3, i3)
 kinds = [afx.ATTR_PUBLIC_SCALAR] * 2 + [afx.ATTR_PUBLIC_POINT] * 2 + [afx.ATTR_SECRET_POINT] * 4
 shape = batch.shape_of_kinds(kinds)
-out = []
+out, out_wire = [], []
 for n in (1, 16):
     z = lambda *s: np.zeros(s, np.uint8)
     pres = {"challenge": z(n, 32), "responses": z(shape.n_responses, n, 32), "C_x_0": z(n, 32), "C_x_1": z(n, 32), "C_V": z(n, 32), "C_y": z(8, n, 32),
@@ -36,7 +39,14 @@ for n in (1, 16):
     for _ in range(%(calls)d):
         batch.verify_presentations(ctx, shape, pres)
     out.append((time.perf_counter() - t0) / %(calls)d * 1e6)
-print("%%.2f %%.2f" %% tuple(out))
+    blob = wire.pack_presentations(shape, pres)
+    for _ in range(50):
+        wire.verify_wire(ctx, blob)
+    t0 = time.perf_counter()
+    for _ in range(%(calls)d):
+        wire.verify_wire(ctx, blob)
+    out_wire.append((time.perf_counter() - t0) / %(calls)d * 1e6)
+print("%%.2f %%.2f %%.2f %%.2f" %% tuple(out + out_wire))
 """
 
 
@@ -58,11 +68,18 @@ def main():
         for name, tree in trees:
             libs[name] = os.path.join(tmp, "libafx_hostsim_%s.so" % name)
             build(tree, libs[name])
-        print("%-6s %-6s %12s %12s" % ("round", "tree", "1 item us", "16 items us"))
+        cols = ("1 item us", "16 items us", "wire 1 us", "wire 16 us")
+        print("%-6s %-6s" % ("round", "tree") + " %12s" * 4 % cols)
+        seen = {name: [] for name, _ in trees}
         for r in range(a.rounds):
             for name, tree in trees:
                 got = subprocess.run([sys.executable, "-c", ROUND % {"tree": tree, "lib": libs[name], "calls": a.calls}], capture_output=True, text=True, cwd=tree, check=True)
-                print("%-6d %-6s %12s %12s" % ((r + 1, name) + tuple(got.stdout.split()[-2:])), flush=True)
+                seen[name].append([float(x) for x in got.stdout.split()[-4:]])
+                print("%-6d %-6s" % (r + 1, name) + " %12.2f" * 4 % tuple(seen[name][-1]), flush=True)
+        for name, _ in trees:
+            by_col = list(zip(*seen[name]))
+            print("%-6s %-6s" % ("median", name) + " %12.2f" * 4 % tuple(statistics.median(c) for c in by_col))
+            print("%-6s %-6s" % ("spread", name) + " %12.2f" * 4 % tuple(max(c) - min(c) for c in by_col))
 
 
 if __name__ == "__main__":
