@@ -1,6 +1,7 @@
 """Damaged tags on the device: the single damages of tests/test_tag_ref.py, one kind per item round-robin over the 300 items of a case
 (tests/tagged_case.py), every item damaged except a stride of honest controls.  The expected status is known by construction -
-damaged => 1, control => 0 (item 2, whose m + n is 0, has failed at the prover and stays 1) - and the yardstick's verdict is checked
+damaged => 1, control => 0 (item 2, whose m + n is 0, has failed at the prover and stays 1); five of the damages leave every value
+intact and break only its encoding (a response or the challenge + l, T with bit 255 set, T as p - s) - and the yardstick's verdict is checked
 on the reference sample as well.  The whole-batch transplant (every tag row moved on by one item) fails every item while the batch as
 shown passes.  Statuses are the same in secret modes 0, 1 and 2, and afx_verify_tag_proofs agrees with the combined call."""
 import numpy as np
@@ -13,8 +14,13 @@ pytestmark = pytest.mark.gpu
 
 ALL = [(k, p, False) for k, p in LAYOUTS] + [(k, p, True) for k, p in STRICT_LAYOUTS]
 IDS = ["%s-p%d%s" % ("".join(map(str, k)), p, "-strict" if s else "") for k, p, s in ALL]
-DAMAGES = ("a bit of T", "n + 1", "n + l", "response z", "response s", "the challenge", "T = identity encoding", "another item's tag")
+DAMAGES = ("a bit of T", "n + 1", "n + l", "response z", "response s", "the challenge", "T = identity encoding", "another item's tag",
+           "response z + l", "response s + l", "challenge + l", "T with bit 255", "T as p - s")
 STRIDE = len(DAMAGES) + 1          # item i carries damage i % STRIDE; the last residue is an honest control
+P = 2 ** 255 - 19
+# ... and of the received C_y[p] row afx_verify_tag_proofs is given, every tag row honest
+CY_DAMAGES = ("C_y[p] + l", "C_y[p] with bit 255", "C_y[p] as p - s")
+CY_STRIDE = len(CY_DAMAGES) + 1
 
 
 @pytest.fixture(scope="module")
@@ -31,6 +37,16 @@ def cases():
     yield get
     for c in made.values():
         c.close()
+
+
+def alias(row, add):
+    """the row's integer + add as 32 bytes: the same value mod l (add = l) or to a decoder that drops bit 255 (add = 2^255)"""
+    return np.frombuffer((int.from_bytes(bytes(row), "little") + add).to_bytes(32, "little"), np.uint8)
+
+
+def negated(row):
+    """p - s: the field element -s, which a decoder without the sign test on s takes for the same point (s = 0 gives p itself)"""
+    return np.frombuffer((P - int.from_bytes(bytes(row), "little")).to_bytes(32, "little"), np.uint8)
 
 
 def damaged_batch(c):
@@ -63,6 +79,16 @@ def damaged_batch(c):
             j = (i + STRIDE) % TOTAL if (i + STRIDE) % TOTAL != FAILING else (i + 2 * STRIDE) % TOTAL
             for f in tg:
                 tg[f][..., i, :] = tags[f][..., j, :]
+        elif k == 8:
+            tg["responses"][0, i] = alias(tags["responses"][0, i], L)
+        elif k == 9:
+            tg["responses"][1, i] = alias(tags["responses"][1, i], L)
+        elif k == 10:
+            tg["challenge"][i] = alias(tags["challenge"][i], L)
+        elif k == 11:
+            tg["T"][i] = alias(tags["T"][i], 2 ** 255)
+        elif k == 12:
+            tg["T"][i] = negated(tags["T"][i])
     want[FAILING] = 1
     return nonce, tg, want
 
@@ -86,10 +112,35 @@ def test_single_damages_fail_and_controls_pass(cases, kinds, p, strict):
     assert batch.verify_tag_proofs(c.user, p, c.H, pres["C_y"][p], nonce, tg).tolist() == want.tolist()
     # the yardstick's verdict on the reference sample
     sp = S.Params(c.params)
-    for i in SAMPLE:
+    for i in sorted(set(SAMPLE) | set(range(3, 3 + STRIDE))):          # (every damage at least once)
         ref = TR.tag_verify(sp, p, c.H, bytes(nonce[i]), bytes(pres["C_y"][p][i]),
                             dict(T=bytes(tg["T"][i]), challenge=bytes(tg["challenge"][i]), responses=[bytes(tg["responses"][k][i]) for k in range(2)]))
         assert ref == int(want[i]), (i, DAMAGES[i % STRIDE] if i % STRIDE < len(DAMAGES) else "control")
+
+
+@pytest.mark.parametrize("kinds,p,strict", ALL, ids=IDS)
+def test_aliases_of_the_received_commitment_fail_the_tag_proof(cases, kinds, p, strict):
+    """afx_verify_tag_proofs on a C_y[p] row whose item i carries CY_DAMAGES[i % CY_STRIDE]: the value is the same point to a decoder
+    that drops bit 255 or skips the sign test, so only the decode of that row refuses it.  The yardstick states the verdict first."""
+    from aeonflux_amd import batch
+    from tests.pyref import statements as S
+    c = cases(kinds, p, strict)
+    pres, tags, shape, st = c.honest
+    Cy = pres["C_y"][p].copy()
+    want = np.zeros(TOTAL, np.uint8)
+    for i in range(TOTAL):
+        k = i % CY_STRIDE
+        if k < len(CY_DAMAGES):
+            want[i] = 1
+            Cy[i] = (alias(Cy[i], L), alias(Cy[i], 2 ** 255), negated(Cy[i]))[k]
+    want[FAILING] = 1
+    sp = S.Params(c.params)
+    for i in sorted(set(SAMPLE) | set(range(3, 3 + CY_STRIDE))):
+        ref = TR.tag_verify(sp, p, c.H, bytes(c.nonce[i]), bytes(Cy[i]),
+                            dict(T=bytes(tags["T"][i]), challenge=bytes(tags["challenge"][i]), responses=[bytes(tags["responses"][k][i]) for k in range(2)]))
+        assert ref == int(want[i]), (i, CY_DAMAGES[i % CY_STRIDE] if i % CY_STRIDE < len(CY_DAMAGES) else "control")
+    got = batch.verify_tag_proofs(c.user, p, c.H, Cy, c.nonce, tags)
+    assert got.tolist() == want.tolist(), [(i, CY_DAMAGES[i % CY_STRIDE] if i % CY_STRIDE < len(CY_DAMAGES) else "control") for i in np.nonzero(got != want)[0]]
 
 
 @pytest.mark.parametrize("kinds,p,strict", ALL, ids=IDS)

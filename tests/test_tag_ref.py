@@ -1,6 +1,7 @@
 """CPU-only: the presentation-tag yardstick (tests/tag_ref.py) against itself.  Honest tags verify; (m + n)*T == H; T depends on (m, n, H)
 alone - not on z, C_y's blinding or the proof's seed; another counter or scope gives another T; and every single damage of a tag is
-rejected: a bit of T, n + 1, the non-canonical n + l, each response, the challenge, T = the identity encoding, another item's tag.
+rejected: a bit of T, n + 1, the non-canonical n + l, each response, the challenge, T = the identity encoding, another item's tag, and the
+aliases that leave every value intact: a response or the challenge + l, T or C_y[p] with bit 255 set or as p - s.
 m + n == 0 (mod l) is refused by the prover."""
 import hashlib
 
@@ -88,6 +89,8 @@ def test_every_single_damage_fails(world):
     it, other = make_item(world, 2, m, 9), make_item(world, 2, R.sc_from_wide(world["take"](64)), 9)
     assert verify(world, it) == S.OK and verify(world, other) == S.OK
     flip = lambda b, bit=0: bytes([b[0] ^ (1 << bit)]) + b[1:]
+    plus = lambda b, k: (int.from_bytes(b, "little") + k).to_bytes(32, "little")
+    P = 2 ** 255 - 19
     T = it["tag"]["T"]
     damages = {
         "a bit of T": dict(T=flip(T, 1)),
@@ -102,6 +105,14 @@ def test_every_single_damage_fails(world):
         "another scope": dict(H=world["H2"]),
         "another item's C_y": dict(Cy=other["Cy"]),
         "another item's tag": dict(other["tag"]),
+        # the same values in another encoding: only a canonicity check (scalars) or the decoder's own checks (points) refuse these
+        "response z + l": dict(responses=[plus(it["tag"]["responses"][0], L), it["tag"]["responses"][1]]),
+        "challenge + l": dict(challenge=plus(it["tag"]["challenge"], L)),
+        "T with bit 255": dict(T=plus(T, 2 ** 255)),
+        "T as p - s": dict(T=(P - int.from_bytes(T, "little")).to_bytes(32, "little")),
+        "C_y[p] + l": dict(Cy=plus(it["Cy"], L)),
+        "C_y[p] with bit 255": dict(Cy=plus(it["Cy"], 2 ** 255)),
+        "C_y[p] as p - s": dict(Cy=(P - int.from_bytes(it["Cy"], "little")).to_bytes(32, "little")),
     }
     for name, over in damages.items():
         over.pop("commitments", None)
