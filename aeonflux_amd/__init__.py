@@ -14,6 +14,7 @@ MAX_ATTRIBUTES = 32
 
 OK, E_BAD_ARGS, E_BAD_PARAMS, E_NO_DEVICE, E_HIP, E_NO_KEY = 0, -1, -2, -3, -4, -5
 E_NO_MEMORY = -6
+E_FULL = -7
 ST_OK, ST_VERIFICATION_FAILURE, ST_MAC_CREATION, ST_NO_SYMMETRIC_KEY, ST_UNDECRYPTABLE = 0, 1, 2, 3, 4
 ATTR_PUBLIC_SCALAR, ATTR_SECRET_SCALAR, ATTR_PUBLIC_POINT, ATTR_EITHER_POINT, ATTR_SECRET_POINT = range(5)
 # afx_ctx_set_plan_variants (tests: the alternatives among a small pass's equivalent plans and kernels)
@@ -417,6 +418,16 @@ def lib():
             for name in ("afx_unblind_issuances_wire_rng", "afx_group_unblind_issuances_wire_rng"):
                 getattr(_LIB, name).argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(DeviceRng), C.POINTER(CredentialOut), C.c_void_p,
                                                 C.c_size_t, C.POINTER(C.c_size_t)]
+        # (the spent-tag set: tagset.cpp)
+        if hasattr(_LIB, "afx_tagset_create"):
+            _LIB.afx_tagset_create.argtypes = [C.c_void_p, C.c_size_t, C.c_char_p, C.POINTER(C.c_void_p)]
+            _LIB.afx_tagset_destroy.argtypes = [C.c_void_p]
+            _LIB.afx_tagset_destroy.restype = None
+            _LIB.afx_tagset_size.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+            for name in ("afx_tagset_spend", "afx_tagset_spend_dev"):
+                getattr(_LIB, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+            for name in ("afx_tagset_contains", "afx_tagset_contains_dev"):
+                getattr(_LIB, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         if hasattr(_LIB, "afx_issuer_keygen"):
             _LIB.afx_issuer_keygen.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p]
     return _LIB

@@ -776,6 +776,66 @@ def verify_tag_proofs_dev(ctx, position, H, C_y_p, nonce, tags, count, status):
     check(lib().afx_verify_tag_proofs_dev(ctx.h, C.byref(stmt), _dptr(C_y_p), C.byref(ts), count, _dptr(status)))
 
 
+# ---- the spent-tag set (include/aeonflux_gpu.h "The spent-tag set") ------------------------------------------------------------
+TAG_FRESH, TAG_SPENT, TAG_SKIPPED = 0, 1, 2
+
+
+class TagSet:
+    """afx_tagset: a set of spent tags on the context's device.  spend() answers as the sequential loop would: per item TAG_SKIPPED
+    (status[i] != 0), TAG_SPENT (in the set already, or an earlier item of this call) or TAG_FRESH (inserted now).  Close it before
+    its context."""
+
+    def __init__(self, ctx, capacity, salt=None):
+        if salt is not None:
+            salt = bytes(salt)
+            assert len(salt) == 32
+        self.ctx = ctx                       # (keeps the context alive for as long as the set)
+        h = C.c_void_p()
+        check(lib().afx_tagset_create(ctx.h, capacity, salt, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            if self.ctx.h:                   # (a context closed first has taken the device buffers' stream with it: nothing left to free safely)
+                lib().afx_tagset_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown
+            pass
+
+    def size(self):
+        """(tags in the set, capacity); waits for the queued calls"""
+        n, cap = C.c_uint64(), C.c_uint64()
+        check(lib().afx_tagset_size(self.h, C.byref(n), C.byref(cap)))
+        return n.value, cap.value
+
+    def spend(self, T, status=None, out=None):
+        """T [count, 32], status [count] or None -> seen [count] (into `out` when given: a refused call leaves it untouched)"""
+        T = _u8(T).reshape(-1, 32)
+        cnt = T.shape[0]
+        st = _u8(status).reshape(cnt) if status is not None else None
+        seen = out if out is not None else np.full(cnt, 255, np.uint8)
+        check(lib().afx_tagset_spend(self.h, T.ctypes.data, st.ctypes.data if st is not None else None, cnt, seen.ctypes.data))
+        return seen
+
+    def contains(self, T):
+        """T [count, 32] -> [count], 1 where the tag is in the set"""
+        T = _u8(T).reshape(-1, 32)
+        seen = np.full(T.shape[0], 255, np.uint8)
+        check(lib().afx_tagset_contains(self.h, T.ctypes.data, T.shape[0], seen.ctypes.data))
+        return seen
+
+    def spend_dev(self, T, status, count, seen):
+        """afx_tagset_spend_dev over device rows (status may be None); asynchronous on the context's stream"""
+        check(lib().afx_tagset_spend_dev(self.h, _dptr(T), _dptr(status), count, _dptr(seen)))
+
+    def contains_dev(self, T, count, seen):
+        check(lib().afx_tagset_contains_dev(self.h, _dptr(T), count, _dptr(seen)))
+
+
 def multiscalar_mul(ctx, scalars, points):
     """out[i] = sum_k scalars[k,i] * points[k,i];  scalars, points: [n_terms, count, 32]"""
     scalars, points = _u8(scalars), _u8(points)

@@ -82,3 +82,8 @@ hipError_t afxk_sc_invert(hipStream_t s, const uint8_t* a, const uint8_t* b, uin
 hipError_t afxk_tag_broadcast(hipStream_t s, const uint8_t* enc, uint8_t* rows, uint32_t count);
 // ok[0] = 1 when the 32 bytes at enc decode (the scope generator of a tagged call), else 0
 hipError_t afxk_tag_scope_check(hipStream_t s, const uint8_t* enc, uint8_t* ok);
+// the spent-tag set (tagset.cuh, the last part of kernels.hip; plan.h afx_tagset_table), direct launches: check-and-insert of T [count][32] in
+// the call's order (k_tagset_claim, then k_tagset_resolve: slot_of [count] is the first launch's word to the second; status_in [count] or
+// null; seen_out [count] AFX_TAG_*), and the lookup alone (seen_out 0 / 1).  Rows 16-byte aligned.  Weak references on the host side.
+hipError_t afxk_tagset_spend(hipStream_t s, const afx_tagset_table* t, const uint8_t* T, const uint8_t* status_in, uint32_t count, uint32_t* slot_of, uint8_t* seen_out);
+hipError_t afxk_tagset_contains(hipStream_t s, const afx_tagset_table* t, const uint8_t* T, uint32_t count, uint8_t* seen_out);

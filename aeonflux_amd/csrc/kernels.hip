@@ -2060,3 +2060,6 @@ hipError_t afxk_encode_to_group(hipStream_t s, const afx_encode_job* jobs, uint3
 
 // presentation tags: the scalar inversion in front of a tagged call's passes and the broadcast of its scope generator
 #include "tags.cuh"
+
+// the spent-tag set: check-and-insert of 32-byte tags in a hash table in HBM, and the lookup alone
+#include "tagset.cuh"

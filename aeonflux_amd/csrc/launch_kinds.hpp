@@ -18,6 +18,7 @@
 //   afxk_draw                                              fake_draw.cpp (device draws)
 //   afxk_encode_at, afxk_msg_gather / _expand / _status    fake_messages.cpp (whole messages)
 //   afxk_sc_invert, afxk_tag_broadcast, _tag_scope_check   fake_tags.cpp (presentation tags)
+//   afxk_tagset_spend, afxk_tagset_contains                nobody yet (the spent-tag set: tests/hostsim/tagset_host.cpp runs the lane bodies themselves)
 hipError_t afxk_coef(hipStream_t s, const afx_coef_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
 hipError_t afxk_mask_rows(hipStream_t s, const afx_mask_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
 hipError_t afxk_sha512_jobs(hipStream_t s, const afx_sha512_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
@@ -32,6 +33,9 @@ hipError_t afxk_msg_status(hipStream_t s, const afx_msgstat_job* job) __attribut
 hipError_t afxk_sc_invert(hipStream_t s, const uint8_t* a, const uint8_t* b, uint8_t* out, uint32_t count) __attribute__((weak));
 hipError_t afxk_tag_broadcast(hipStream_t s, const uint8_t* enc, uint8_t* rows, uint32_t count) __attribute__((weak));
 hipError_t afxk_tag_scope_check(hipStream_t s, const uint8_t* enc, uint8_t* ok) __attribute__((weak));
+hipError_t afxk_tagset_spend(hipStream_t s, const afx_tagset_table* t, const uint8_t* T, const uint8_t* status_in, uint32_t count, uint32_t* slot_of, uint8_t* seen_out)
+    __attribute__((weak));
+hipError_t afxk_tagset_contains(hipStream_t s, const afx_tagset_table* t, const uint8_t* T, uint32_t count, uint8_t* seen_out) __attribute__((weak));
 
 namespace afx {
 

@@ -396,3 +396,22 @@ typedef struct {
   uint8_t* trace;                  /* optional [count][32]: the recomputed challenge is also stored here (parity aid) */
   uint32_t n_fields, n_outs;       /* host only: entries of the `fields` / `outs` pointer tables (Plan::relocate walks them)  */
 } afx_hash_program;
+
+/* The spent-tag set (include/aeonflux_gpu.h "The spent-tag set"; tagset.cuh): the table as its kernels see it.  Open addressing, linear
+ * probing with wrap-around, n_slots = mask + 1 a power of two.  Struct of arrays; `owner` and `lowest` are touched with device-scope
+ * atomics only while a launch runs, `keys` is written by k_tagset_resolve and read by LATER launches. */
+#define AFX_TAGSET_EMPTY 0xffffffffu   /* owner: nobody                                                    */
+#define AFX_TAGSET_KEPT 0xfffffffeu    /* owner: keys[slot] holds a tag of an earlier call                 */
+/* slot_of[item], the claim launch's word to the resolve launch: a slot, or one of */
+#define AFX_TAGSET_NO_SLOT 0xffffffffu /* the probe ran over the whole table (the error word is set)        */
+#define AFX_TAGSET_OLD 0xfffffffeu     /* the tag was in the set before this call                           */
+#define AFX_TAGSET_SKIP 0xfffffffdu    /* status_in[item] != 0                                              */
+typedef struct {
+  uint8_t* keys;                /* [n_slots][32], 16-byte aligned                                          */
+  uint32_t* owner;              /* [n_slots]: AFX_TAGSET_EMPTY, AFX_TAGSET_KEPT or an item of the running call */
+  uint32_t* lowest;             /* [n_slots]: the lowest item of the running call that ended at the slot    */
+  unsigned long long* words;    /* [0] tags in the set, [1] error word (not 0: the set is unusable)         */
+  uint64_t salt[4];             /* the 32 salt bytes as little-endian words                                 */
+  uint32_t mask;                /* n_slots - 1                                                              */
+  uint32_t pad;
+} afx_tagset_table;

@@ -44,6 +44,7 @@ extern "C" {
 #define AFX_E_HIP (-4)         /* a HIP runtime call failed; see afx_last_error()                 */
 #define AFX_E_NO_KEY (-5)      /* operation needs the issuer secret key but ctx has none          */
 #define AFX_E_NO_MEMORY (-6)   /* host allocation (or thread creation) failed inside the library    */
+#define AFX_E_FULL (-7)        /* a spent-tag set cannot be sure to hold this call's tags (afx_tagset_*) */
 
 /* per-item status == the reference's CredentialError outcome (src/errors.rs:73-89) */
 #define AFX_ST_OK 0
@@ -974,7 +975,7 @@ int afx_unblind_issuances_dev(afx_ctx* ctx, const afx_attributes_soa* attrs, con
  *
  * Why T is bound to the credential.  Constraint 1 extracts (z', s) with C_y[p] = z'*G_y[p] + (s - n)*G_m[p]; the presentation proof
  * extracts (z, m) for the same C_y[p]; binding under the discrete logarithm between G_y[p] and G_m[p] gives s = m + n; constraint 2
- * then fixes T = (m + n)^-1 * H.  Detecting equal T is the caller's set lookup: the library keeps no store of tags.
+ * then fixes T = (m + n)^-1 * H.  Detecting equal T is a set lookup: afx_tagset (below) keeps such a set on the device.
  *
  * Secrets.  m, s and s^-1: the show is a prover-side plan under the context's secret-independent addressing like afx_show; s^-1 is made
  * by a kernel whose instruction stream and addresses do not depend on s (Fermat's inverse over the bits of the public l - 2), and the
@@ -990,7 +991,7 @@ int afx_unblind_issuances_dev(afx_ctx* ctx, const afx_attributes_soa* attrs, con
  * copy nothing and wait for nothing from the second call on each lane on (with afx_ctx_set_pipelining calls alternate between two lanes,
  * each of which copies H once), until a call needs a larger buffer: the buffer that replaces it receives H again.
  * Out of scope: a wire format for tagged presentations, afx_group_* forms, _rng draws of tag_seed, the batchable encoding of the tag
- * proof, mixed layouts and coalescing, the Rust shim, bench.py, any duplicate-tag store. */
+ * proof, mixed layouts and coalescing, the Rust shim, bench.py. */
 /* (declared apart from their typedefs, like afx_device_rng: the Rust shim does not bind them) */
 struct afx_tag_statement {
   uint32_t position;               /* p                                            */
@@ -1028,6 +1029,51 @@ int afx_verify_presentations_tagged_dev(afx_ctx* ctx, const afx_shape* shape, co
 int afx_verify_tag_proofs(afx_ctx* ctx, const afx_tag_statement* tag, const uint8_t* C_y_p, const afx_tags_soa* tags, size_t count, uint8_t* status);
 int afx_verify_tag_proofs_dev(afx_ctx* ctx, const afx_tag_statement* tag, const uint8_t* C_y_p, const afx_tags_soa* tags, size_t count,
                               uint8_t* status_dev);
+
+/* ---- The spent-tag set: check-and-insert of tags on the device ----------------------------------
+ * "At most N shows per credential and scope" is n < N plus a set lookup on T.  An afx_tagset is that set, kept in HBM beside the rows a
+ * tagged verification has just written: one call marks a batch of tags spent and says which of them were spent already.  Off unless
+ * called: nothing above changes.
+ *
+ * Semantics of afx_tagset_spend (normative): the call answers as this loop would, for i = 0 .. count - 1 IN ORDER:
+ *   - status_in given and status_in[i] != 0:   seen_out[i] = AFX_TAG_SKIPPED, nothing inserted (an item that failed verification);
+ *   - else the 32 bytes T[i] are in the set:   seen_out[i] = AFX_TAG_SPENT;
+ *   - else                                     seen_out[i] = AFX_TAG_FRESH and T[i] is inserted.
+ * So among equal tags of one call the lowest index is the fresh one, whatever order the hardware takes them in.  Tags are compared as
+ * the 32 bytes given, with no decoding (a tag that passed verification is canonical already).  afx_tagset_contains looks up and inserts
+ * nothing: seen_out[i] = 1 iff T[i] is in the set.
+ *
+ * Capacity.  The set holds at most `capacity` tags (1 .. 2^30).  A call is refused with AFX_E_FULL, before anything is read or written,
+ * unless (the known upper bound of the size) + count <= capacity, skipped items included: the host cannot know how many of a call's
+ * tags are new before it runs.  The host forms refresh the exact size after every call; after _dev calls the bound is the last exact
+ * size plus the counts since, until afx_tagset_size (which waits for the queued calls) refreshes it.  count > 2^32 - 3: AFX_E_BAD_ARGS.
+ *
+ * Layout and slot function (normative, so that tests can aim at slots).  n_slots = the smallest power of two >= 2 * capacity; open
+ * addressing, linear probing with wrap-around;
+ *   slot(T) = u64le( SHAKE256("aeonflux-amd/tagset/v1" (22 ASCII bytes) || salt (32) || T (32)) [0..8) ) mod n_slots
+ * The salt (the caller's 32 bytes, or getrandom(2) for NULL) keeps a user who picks their own hidden scalar from aiming tags at one probe
+ * chain; the answers do not depend on it.  Memory: 40 bytes per slot.
+ *
+ * Conventions.  A set belongs to the context it was created on (and to its device) and is destroyed BEFORE that context.  The host
+ * forms take the context in turn and stage a call in one piece.  `_dev`: device pointers, rows 16-byte aligned, the call asynchronous on
+ * afx_ctx_stream (with afx_ctx_set_pipelining calls alternate between two lanes; calls on one set are ordered behind each other on the
+ * device whichever lane they take).  A HIP failure inside a call, or a table the kernels find inconsistent, leaves the set unusable:
+ * every later call returns the first error.  No lane of the kernels ever waits for another lane (tagset.cuh).
+ * Out of scope: removal, export and import of a set (a server that must survive a restart logs the tags it accepted). */
+typedef struct afx_tagset afx_tagset;
+#define AFX_TAG_FRESH 0
+#define AFX_TAG_SPENT 1
+#define AFX_TAG_SKIPPED 2
+/* salt: 32 bytes or NULL (getrandom); capacity is a size_t like every count of this header */
+int afx_tagset_create(afx_ctx* ctx, size_t capacity, const uint8_t* salt, afx_tagset** out);
+void afx_tagset_destroy(afx_tagset* set);
+/* waits for the queued calls; either output may be NULL */
+int afx_tagset_size(afx_tagset* set, uint64_t* size_out, uint64_t* capacity_out);
+/* T: [count][32]; status_in: [count] or NULL; seen_out: [count] */
+int afx_tagset_spend(afx_tagset* set, const uint8_t* T, const uint8_t* status_in, size_t count, uint8_t* seen_out);
+int afx_tagset_spend_dev(afx_tagset* set, const uint8_t* T, const uint8_t* status_in, size_t count, uint8_t* seen_out);
+int afx_tagset_contains(afx_tagset* set, const uint8_t* T, size_t count, uint8_t* seen_out);
+int afx_tagset_contains_dev(afx_tagset* set, const uint8_t* T, size_t count, uint8_t* seen_out);
 
 /* ---- Blind issuance on bytes: AFXQ requests in, AFXJ issuances out ----------------------------
  * The issuer's side of the section above with the two doors the plain issuer has (afx_issue_wire, afx_issue_wire_rng): serialized
