@@ -18,7 +18,7 @@
 //   afxk_draw                                              fake_draw.cpp (device draws)
 //   afxk_encode_at, afxk_msg_gather / _expand / _status    fake_messages.cpp (whole messages)
 //   afxk_sc_invert, afxk_tag_broadcast, _tag_scope_check   fake_tags.cpp (presentation tags)
-//   afxk_tagset_spend, afxk_tagset_contains                nobody yet (the spent-tag set: tests/hostsim/tagset_host.cpp runs the lane bodies themselves)
+//   afxk_tagset_spend, afxk_tagset_contains                fake_tagset.cpp (the spent-tag set: it runs tagset.cuh's lane bodies, as tests/hostsim/tagset_host.cpp does)
 hipError_t afxk_coef(hipStream_t s, const afx_coef_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
 hipError_t afxk_mask_rows(hipStream_t s, const afx_mask_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));
 hipError_t afxk_sha512_jobs(hipStream_t s, const afx_sha512_job* jobs, uint32_t njobs, const afx_row* rows, const afx_pass* passes, uint32_t max_count) __attribute__((weak));

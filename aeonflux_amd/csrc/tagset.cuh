@@ -20,7 +20,8 @@
 //
 // The per-lane bodies (tagset_slot, tagset_claim_item, tagset_resolve_item, tagset_contains_item) are plain C++ over four atomics
 // (TS_CAS, TS_MIN, TS_OR, TS_ADD): tests/hostsim/tagset_host.cpp compiles these very statements for the host and runs them lane by
-// lane in shuffled orders.  The kernels and their launchers need the HIP compiler.
+// lane in shuffled orders, and on threads under ThreadSanitizer; tests/hostsim/fake_tagset.cpp runs them behind tagset.cpp.  The
+// kernels and their launchers need the HIP compiler.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,6 +34,22 @@
 #define TS_MIN(p, v) atomicMin((p), (v))
 #define TS_OR(p, v) atomicOr((p), (v))
 #define TS_ADD(p, v) atomicAdd((p), (v))
+#elif defined(AFX_TAGSET_TEST_THREADS)
+// a host build whose lanes run on threads (only tests/hostsim/tagset_host.cpp defines the macro): the four as relaxed atomics, which is
+// all the device's are - ordering between the launches comes from the stream there and from joining the threads here
+static inline uint32_t ts_host_cas(uint32_t* p, uint32_t expected, uint32_t desired) {
+  __atomic_compare_exchange_n(p, &expected, desired, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
+  return expected;   // (the builtin leaves the word's value here when it differs)
+}
+static inline uint32_t ts_host_min(uint32_t* p, uint32_t v) {
+  uint32_t old = __atomic_load_n(p, __ATOMIC_RELAXED);
+  while (v < old && !__atomic_compare_exchange_n(p, &old, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+  return old;
+}
+#define TS_CAS(p, expected, desired) ts_host_cas((p), (uint32_t)(expected), (uint32_t)(desired))
+#define TS_MIN(p, v) ts_host_min((p), (uint32_t)(v))
+#define TS_OR(p, v) __atomic_fetch_or((p), (v), __ATOMIC_RELAXED)
+#define TS_ADD(p, v) __atomic_fetch_add((p), (v), __ATOMIC_RELAXED)
 #else
 // the host build runs one lane at a time (each order of whole lanes is one legal interleaving)
 template <class T> static inline T ts_host_cas(T* p, T expected, T desired) { const T old = *p; if (old == expected) *p = desired; return old; }

@@ -1,6 +1,7 @@
 """The spent-tag set's model (include/aeonflux_gpu.h "The spent-tag set"): the slot function on hashlib, the sequential loop that
 afx_tagset_spend is specified to equal, and tags aimed at slots - arbitrary 32-byte strings, no group arithmetic.  Shared by
-tests/test_tagset_on_host.py (the lane bodies on the host) and tests/test_gpu_tagset.py (the kernels)."""
+tests/test_tagset_on_host.py (the lane bodies on the host), tests/test_hostsim_tagset.py (tagset.cpp on the fake runtime),
+tests/test_gpu_tagset.py (the kernels) and tests/test_gpu_rate_limit.py (the loop alone, on keys of its own)."""
 import hashlib
 
 FRESH, SPENT, SKIPPED = 0, 1, 2
@@ -130,9 +131,82 @@ def case_fill():
     return 64, [("spend", tags, None), ("contains", tags[::9] + [tag("fill absent")])]
 
 
+def case_near_tags():
+    """pairs of tags that differ in ONE of their eight 32-bit words and start at one slot: the only place where a comparison that skips
+    a word shows - tags that differ anywhere nearly always start apart and are never compared.  The second of a pair meets the first as
+    an item of its own call, and in the next calls as a kept key"""
+    first, second = [], []
+    for word in range(8):
+        base = tag("near %d" % word)
+        k = 0
+        while True:
+            other = base[:4 * word] + hashlib.shake_256(b"near other %d" % k).digest(4) + base[4 * word + 4:]
+            k += 1
+            if other != base and slot(SALT, other, 128) == slot(SALT, base, 128):
+                break
+        first += [base, other]
+        second += [other[:4 * word] + bytes(b ^ 0x80 for b in other[4 * word:4 * word + 4]) + other[4 * word + 4:]]      # a third of the family, wherever it starts
+    return 64, [("spend", first, None), ("contains", first + second), ("spend", first[1::2] + first[::2], None), ("spend", second, None)]
+
+
+# Nine workgroups of AFX_BLOCK = 256 lanes: more than the MI355X has XCDs, so some of one key's items run on dies with private L2s and
+# meet only in `owner` and `lowest`.  8192 slots, the table of capacity = count.
+WIDE = 2304
+WIDE_KINDS = ("one tag", "every block", "every block, lowest skipped", "descending pairs")
+
+
+def case_wide(kind):
+    """2304 items, then the whole call again (all spent, or skipped), then a lookup"""
+    n = WIDE
+    status = None
+    if kind == "one tag":
+        tags = [tag("wide one")] * n
+    elif kind in ("every block", "every block, lowest skipped"):
+        tags = [tag("wide %d" % (i % 257)) for i in range(n)]           # 257: each key has an item in every workgroup, at a lane that moves
+        if kind.endswith("skipped"):
+            status = [3 if i < 257 else 0 for i in range(n)]            # the lowest index of every key is out: the second lowest is fresh
+    else:
+        tags = [tag("wide pair %d" % ((n - 1 - i) // 2)) for i in range(n)]
+    probe = tags[::97] + [tag("wide absent %d" % k) for k in range(3)]
+    # the replay is refused unless size + count <= capacity: the smallest capacity that takes it, still 8192 slots
+    capacity = n + len(set(tags))
+    assert n_slots(capacity) == n_slots(n)
+    return capacity, [("spend", tags, status), ("spend", tags, status), ("contains", probe)]
+
+
+_wide_chain = []
+
+
+def case_wide_chain():
+    """24 tags whose probe sequences start at one slot, each once in every one of nine workgroups, among tags that go anywhere"""
+    slots = n_slots(WIDE)
+    if not _wide_chain:
+        _wide_chain.extend(tags_at(SALT, slots, 4097, 24, "wide chain"))
+    tags = [tag("wide filler %d" % i) for i in range(WIDE)]
+    for w in range(WIDE // 256):
+        for k, t in enumerate(_wide_chain):
+            tags[256 * w + (10 * k + 7 * w) % 256] = t                   # (10 * k < 256: 24 lanes of the workgroup, other ones in each)
+    return WIDE, [("spend", tags, None), ("contains", _wide_chain + [tag("wide chain absent")]), ("spend", _wide_chain[::-1], None)]
+
+
 CASES = dict([("count %d" % n, (lambda n=n: case_count(n))) for n in COUNTS] +
              [("duplicates", case_duplicates), ("one start slot", case_one_start_slot), ("wrap", case_wrap), ("skipped", case_skipped),
-              ("replays", case_replays), ("fill", case_fill)])
+              ("replays", case_replays), ("fill", case_fill), ("near tags", case_near_tags)] +
+             [("wide: %s" % k, (lambda k=k: case_wide(k))) for k in WIDE_KINDS] + [("wide: one start slot", case_wide_chain)])
+
+
+def scenario_text(capacity, salt, ops):
+    """a case as the text the host programs read (tests/hostsim/tagset_host.cpp, tests/hostsim/tagset_doors.cpp)"""
+    lines = ["set %d %s" % (capacity, salt.hex())]
+    for op in ops:
+        if op[0] == "spend":
+            status = op[2] if op[2] is not None else [0] * len(op[1])
+            lines.append("call %d" % len(op[1]))
+            lines += ["%s %d" % (t.hex(), s) for t, s in zip(op[1], status)]
+        else:
+            lines.append("contains %d" % len(op[1]))
+            lines += [t.hex() for t in op[1]]
+    return "\n".join(lines) + "\n"
 
 
 def expected(ops):

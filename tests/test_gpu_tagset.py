@@ -8,7 +8,13 @@ lane 255 - the last lane of the first block - the lowest index of two groups; 40
 interleaved with repeats; a chain from slot 126 over the wrap to slot 0; items skipped by status_in on both sides of a participating
 repeat; second and third calls that replay parts of the first; lookups before and after; a fill to exactly the capacity.
 Capacity 64 (128 slots) wherever the calls fit it: a call is refused unless size + count <= capacity, so the counts above 64 run on
-the smallest set that takes them (capacity = count)."""
+the smallest set that takes them (capacity = count).
+
+Where 300 items do not reach: 2304 items, nine workgroups - more than the device has XCDs, whose L2s are private, so lanes of one key
+meet only in `owner` and `lowest` across dies - with one tag for all, with a key in every workgroup, with the lowest index of every
+key skipped, with descending pairs, and with a 24-slot chain whose items lie in all nine; pairs of tags that differ in one word and
+share a start slot.  Beside the cases: _dev rows at an address that is 16 mod 32 with status and answers at odd addresses (ts_load is
+two 16-byte loads), and the bytes on both sides of the answers."""
 import numpy as np
 import pytest
 
@@ -149,6 +155,88 @@ def test_the_dev_forms_on_both_pipelining_lanes_give_the_same_bytes(ctx):
         finally:
             ts.close()
             ctx.set_pipelining(0)
+
+
+class DevAt:
+    """`nbytes` of device memory that start `offset` bytes into an allocation with `after` more bytes behind them, all of it 0xEE first"""
+
+    def __init__(self, offset, nbytes, after=0, array=None):
+        from tests.helpers import DevMem
+        self.mem = DevMem(nbytes=offset + nbytes + after, fill=0xEE)
+        self.offset, self.n, self.ptr = offset, nbytes, self.mem.ptr + offset
+        if array is not None:
+            a = np.ascontiguousarray(array, dtype=np.uint8)
+            assert a.nbytes == nbytes
+            assert self.mem.hip().hipMemcpy(self.ptr, a.ctypes.data, a.nbytes, 1) == 0
+
+    def parts(self):
+        whole = self.mem.numpy()
+        return whole[:self.offset], whole[self.offset:self.offset + self.n], whole[self.offset + self.n:]
+
+
+def dev_ops(ctx, ts, ops, t_off, b_off):
+    """the ops through the _dev forms, every call queued before anything is read: rows t_off bytes and status / answers b_off bytes into
+    their (256-byte aligned) allocations.  -> the answers, with the bytes around them checked"""
+    bufs = []
+    for op in ops:
+        n = len(op[1])
+        d_T, d_seen = DevAt(t_off, 32 * n, array=rows(op[1])), DevAt(b_off, n, after=3)
+        if op[0] == "spend":
+            d_st = None if op[2] is None else DevAt(b_off, n, array=np.array(op[2], np.uint8))
+            ts.spend_dev(d_T.ptr, None if d_st is None else d_st.ptr, n, d_seen.ptr)
+            bufs.append((d_T, d_st, d_seen))
+        else:
+            ts.contains_dev(d_T.ptr, n, d_seen.ptr)
+            bufs.append((d_T, d_seen))
+    ctx.synchronize()
+    out = []
+    for b in bufs:
+        before, seen, after = b[-1].parts()
+        assert before.tolist() == [0xEE] * b_off and after.tolist() == [0xEE] * 3
+        out.append(seen.tolist())
+    return out
+
+
+@pytest.mark.parametrize("name", ["skipped", "duplicates"])
+def test_rows_at_16_mod_32_and_bytes_at_odd_addresses_give_the_aligned_calls_answers(ctx, name):
+    """ts_load reads a row as two 16-byte halves: a row needs 16-byte alignment and no more.  status_in and seen_out are bytes"""
+    from aeonflux_amd import batch
+    capacity, ops = M.CASES[name]()
+    want, tags = M.expected(ops)
+    got = {}
+    for t_off, b_off in ((0, 0), (16, 1), (48, 3)):
+        ts = batch.TagSet(ctx, capacity, M.SALT)
+        try:
+            got[t_off] = dev_ops(ctx, ts, ops, t_off, b_off)
+            assert ts.size() == (len(tags), capacity)
+        finally:
+            ts.close()
+    assert got[0] == want
+    assert got[16] == got[0] and got[48] == got[0]
+
+
+@pytest.mark.parametrize("count", [1, 65, 257])
+def test_the_bytes_around_the_answers_are_untouched(ctx, count):
+    from aeonflux_amd import batch
+    tags = [M.tag("around %d" % (i % max(1, count - 2))) for i in range(count)]           # (with repeats at the end when there is room)
+    status = [1 if i % 5 == 4 else 0 for i in range(count)]
+    ts = batch.TagSet(ctx, max(64, 2 * count), M.SALT)
+    try:
+        m = M.Model()
+        d_T, d_st = DevAt(0, 32 * count, array=rows(tags)), DevAt(0, count, array=np.array(status, np.uint8))
+        seen = [DevAt(64, count, after=64) for _ in range(3)]
+        ts.spend_dev(d_T.ptr, d_st.ptr, count, seen[0].ptr)
+        ts.contains_dev(d_T.ptr, count, seen[1].ptr)
+        ts.spend_dev(d_T.ptr, None, count, seen[2].ptr)
+        ctx.synchronize()
+        want = [m.spend(tags, status), m.contains(tags), m.spend(tags)]
+        for s, w in zip(seen, want):
+            before, got, after = s.parts()
+            assert got.tolist() == w
+            assert before.tolist() == [0xEE] * 64 and after.tolist() == [0xEE] * 64
+        assert ts.size() == (len(m.tags), max(64, 2 * count))
+    finally:
+        ts.close()
 
 
 def test_dev_calls_count_towards_the_bound_until_the_size_is_read(ctx):

@@ -8,7 +8,15 @@ interleaving at lane granularity:
     seen_out     identical across the orders (the program's own check) and equal to the sequential loop of the header
     the contents identical across the orders as a set, equal to the model's set; the size word is their number
 
-on the cases of tests/tagset_model.py, which tests/test_gpu_tagset.py runs on the kernels."""
+on the cases of tests/tagset_model.py, which tests/test_gpu_tagset.py runs on the kernels.
+
+Lane by lane, a lane that joins a slot always finds the claimer's minimum done.  So the same program is built a second time with
+-DAFX_TAGSET_TEST_THREADS -fsanitize=thread: the header's atomics are then relaxed __atomic builtins, and the claim lanes of a call run
+on 16 threads, are joined, and the resolve lanes run on 16 threads - 20 rounds a case, each from a fresh table, with the same checks
+and ThreadSanitizer watching the lane bodies.
+
+`tagset_host error-paths` (the first build) runs the lane bodies on tables no finished call leaves: a stale owner on a probe path, and
+a table without an empty slot."""
 import os
 import subprocess
 
@@ -19,30 +27,28 @@ from tests import tagset_model as M
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("tagset") / "tagset_host")
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I" + os.path.join(ROOT, "tests", "hostsim", "include"),
-           "-o", out, os.path.join(ROOT, "tests", "hostsim", "tagset_host.cpp")]
+def compile_program(out, flags):
+    cmd = ["g++", "-O1", "-g", "-std=c++17"] + flags + ["-I" + os.path.join(ROOT, "tests", "hostsim", "include"), "-o", out, os.path.join(ROOT, "tests", "hostsim", "tagset_host.cpp")]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     return out
 
 
+@pytest.fixture(scope="module")
+def program(tmp_path_factory):
+    return compile_program(str(tmp_path_factory.mktemp("tagset") / "tagset_host"), ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+
+
+@pytest.fixture(scope="module")
+def threaded_program(tmp_path_factory):
+    return compile_program(str(tmp_path_factory.mktemp("tagset_threads") / "tagset_host"), ["-fsanitize=thread", "-DAFX_TAGSET_TEST_THREADS", "-pthread"])
+
+
 def run(program, tmp_path, capacity, salt, ops):
-    lines = ["set %d %s" % (capacity, salt.hex())]
-    for op in ops:
-        if op[0] == "spend":
-            status = op[2] if op[2] is not None else [0] * len(op[1])
-            lines.append("call %d" % len(op[1]))
-            lines += ["%s %d" % (t.hex(), s) for t, s in zip(op[1], status)]
-        else:
-            lines.append("contains %d" % len(op[1]))
-            lines += [t.hex() for t in op[1]]
     path = tmp_path / "scenario.txt"
-    path.write_text("\n".join(lines) + "\n")
+    path.write_text(M.scenario_text(capacity, salt, ops))
     r = subprocess.run([program, str(path)], capture_output=True, text=True)
-    assert r.returncode == 0, (r.stdout[-500:], r.stderr[-3000:])
+    assert r.returncode == 0 and "Sanitizer" not in r.stderr, (r.stdout[-500:], r.stderr[-3000:])
     slots, answers, keys, size = [], [], set(), None
     for line in r.stdout.split("\n"):
         w = line.split()
@@ -72,6 +78,24 @@ def test_every_lane_order_gives_the_sequential_loops_answers(program, tmp_path, 
         assert s == M.slot(M.SALT, t, n), t.hex()
 
 
+THREADED = ["duplicates", "one start slot", "wrap", "skipped", "near tags"] + [name for name in M.CASES if name.startswith("wide: ")]
+
+
+@pytest.mark.parametrize("name", THREADED)
+def test_lanes_on_threads_give_the_sequential_loops_answers_every_round(threaded_program, tmp_path, name):
+    """(the program compares its 20 rounds with each other; round 0 is compared with the model here)"""
+    capacity, ops = M.CASES[name]()
+    slots, answers, keys, size = run(threaded_program, tmp_path, capacity, M.SALT, ops)
+    want, tags = M.expected(ops)
+    assert answers == want
+    assert keys == tags and size == len(tags)
+
+
+def test_the_lane_bodies_on_a_stale_owner_and_on_a_table_without_an_empty_slot(program):
+    r = subprocess.run([program, "error-paths"], capture_output=True, text=True)
+    assert r.returncode == 0 and "error paths ok" in r.stdout and "Sanitizer" not in r.stderr, (r.stdout[-500:], r.stderr[-3000:])
+
+
 def test_the_slot_function_is_the_headers_on_edge_bytes(program, tmp_path):
     # all-zero and all-ones salts and tags, single set bits at the byte positions where the 86-byte message crosses the sponge's lanes
     tags = [bytes(32), b"\xff" * 32] + [bytes([0] * k + [0x80] + [0] * (31 - k)) for k in (0, 1, 2, 7, 8, 9, 15, 16, 23, 24, 30, 31)] + [bytes(range(32))]
@@ -90,3 +114,8 @@ def test_the_aimed_tags_really_share_their_chains():
     assert {M.slot(M.SALT, t, 128) for t in ops[0][1]} == {37} and len(set(ops[0][1])) == 40
     _, ops = M.case_wrap()
     assert {M.slot(M.SALT, t, 128) for t in ops[0][1]} == {126} and len(set(ops[0][1])) == 5
+    capacity, ops = M.case_wide_chain()
+    chain = ops[1][1][:-1]
+    assert M.n_slots(capacity) == 8192 and len(set(chain)) == 24 and {M.slot(M.SALT, t, 8192) for t in chain} == {4097}
+    for w in range(9):                                                         # each of them once in every workgroup
+        assert sorted(t for t in ops[0][1][256 * w:256 * w + 256] if t in chain) == sorted(chain)
