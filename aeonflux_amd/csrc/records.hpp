@@ -1,6 +1,7 @@
 // Records to struct-of-arrays rows and back on the GPU (kernels.hip k_aos_to_soa, k_soa_to_aos), in one place for every door that
 // reads or writes serialized records: the cell -> row maps, and the two launches with what a collected call asks of them.  Nothing
-// here stages anything: the Stager calls - and their order, which is the staging layout - stay with each door.
+// here stages anything: the Stager calls - and their order, which is the staging layout - stay with each door (batch_arrays.hpp walks
+// a column struct's arrays for them, through the door's own callable).
 #pragma once
 #include "kernels.h"
 #include "statements.hpp"

@@ -16,6 +16,7 @@
 #include "engine.hpp"
 #include <stdlib.h>
 #include "doors.hpp"
+#include "batch_arrays.hpp"
 
 using namespace afx;
 
@@ -751,13 +752,7 @@ int verify_presentations_dev_impl(afx_ctx* ctx, const afx_shape* shape, const af
     uint32_t keep[AFX_MAX_ATTRIBUTES], pos[AFX_MAX_ATTRIBUTES], k = 0;
     int slot[AFX_MAX_ATTRIBUTES];
     if (!presentation_shape_rejects(ctx, sh, keep, &k, slot, pos)) {
-      bool missing = !b.challenge || !b.C_x_0 || !b.C_x_1 || !b.C_V || (sh.n_attributes && !b.C_y) || (sh.n_responses && !b.responses);
-      for (uint32_t i = 0; i < sh.n_attributes; i++)
-        if ((sh.kinds[i] == AFX_ENC_PUBLIC_SCALAR || sh.kinds[i] == AFX_ENC_PUBLIC_POINT) && !b.attr_values) missing = true;
-      for (uint32_t e = 0; e < sh.n_enc_proofs; e++) {
-        const afx_encproof_soa& q = b.enc[e];
-        missing |= !q.challenge || !q.responses || !q.pk || !q.E1 || !q.E2 || !q.C_y_1 || !q.C_y_2 || !q.C_y_3 || !q.C_y_2p;
-      }
+      bool missing = any_null_with_proofs(b, dims_of(sh));
       if (tag && tagged_shape_ok(ctx, sh, tag->position)) missing |= !tag->H_rows || !tag->nonce || !tag->T || !tag->challenge || !tag->responses;
       if (missing) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
     }
@@ -856,15 +851,7 @@ extern "C" int afx_verify_presentations_batchable_dev(afx_ctx* ctx, const afx_sh
   const uint32_t n_main = afx_batchable_main_commitments(ctx, &sh);
   std::vector<const uint8_t*> cenc;
   if (n_main) {   // (0: a shape every item fails on, which reads no array)
-    bool missing = !b.C_x_0 || !b.C_x_1 || !b.C_V || (sh.n_attributes && !b.C_y) || (sh.n_responses && !b.responses) || !commitments->main ||
-                   (sh.n_enc_proofs && !commitments->enc);
-    for (uint32_t i = 0; i < sh.n_attributes; i++)
-      if ((sh.kinds[i] == AFX_ENC_PUBLIC_SCALAR || sh.kinds[i] == AFX_ENC_PUBLIC_POINT) && !b.attr_values) missing = true;
-    for (uint32_t e = 0; e < sh.n_enc_proofs && !missing; e++) {
-      const afx_encproof_soa& q = b.enc[e];
-      missing |= !q.responses || !q.pk || !q.E1 || !q.E2 || !q.C_y_1 || !q.C_y_2 || !q.C_y_3 || !q.C_y_2p || !commitments->enc[e];
-    }
-    if (missing) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
+    if (batchable_any_null(b, *commitments, dims_of(sh))) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
     for (uint32_t e = 0; e < sh.n_enc_proofs; e++) cenc.push_back(commitments->enc[e]);
   }
   std::vector<afx_encproof_soa> encs;
@@ -892,41 +879,31 @@ extern "C" int afx_verify_presentations_batchable(afx_ctx* ctx, const afx_shape*
   if (!ctx->has_key) { set_error("Issuer::verify needs the issuer key"); return AFX_E_NO_KEY; }
   const uint32_t n_main = afx_batchable_main_commitments(ctx, shape);
   if (!n_main) { memset(status, AFX_ST_VERIFICATION_FAILURE, count); return AFX_OK; }   // a shape every item fails on: no array is read
-  const uint32_t na = shape->n_attributes, nr = shape->n_responses, ne = shape->n_enc_proofs;
-  bool missing = !b->C_x_0 || !b->C_x_1 || !b->C_V || (na && !b->C_y) || (nr && !b->responses) || (ne && (!b->enc || !cm->enc)) || !cm->main;
-  for (uint32_t i = 0; i < na; i++)
-    if ((shape->kinds[i] == AFX_ENC_PUBLIC_SCALAR || shape->kinds[i] == AFX_ENC_PUBLIC_POINT) && !b->attr_values) missing = true;
-  for (uint32_t e = 0; e < ne && !missing; e++) {
-    const afx_encproof_soa& q = b->enc[e];
-    missing |= !q.responses || !q.pk || !q.E1 || !q.E2 || !q.C_y_1 || !q.C_y_2 || !q.C_y_3 || !q.C_y_2p || !cm->enc[e];
+  const Dims dm = dims_of(*shape);
+  if (batchable_any_null(*b, *cm, dm)) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
+  // one pass of staging for the whole call (the sliced, two-lane pipe of afx_verify_presentations is not built for this form):
+  // the main arrays without the challenge, the main commitments, then per proof its commitments in the challenge's place
+  HostCall hc(ctx, count, 0);
+  auto in = [&](const uint8_t* p, size_t rows, size_t elem) { const size_t o = hc.in(p, rows, elem); return p ? o : NO_ARRAY; };
+  const Offsets<afx_presentation_soa> om = stage(*b, dm, in, NO_CHALLENGE);
+  const size_t o_cm = hc.in(cm->main, n_main);
+  std::vector<Offsets<afx_encproof_soa>> oe(dm.proofs);
+  std::vector<size_t> o_ce(dm.proofs);
+  for (uint32_t e = 0; e < dm.proofs; e++) {
+    o_ce[e] = hc.in(cm->enc[e], CM_ENC_ROWS);
+    stage(oe[e], b->enc[e], dm, in, NO_CHALLENGE);
   }
-  if (missing) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
-  // one pass of staging for the whole call (the sliced, two-lane pipe of afx_verify_presentations is not built for this form)
-  Stager st(ctx);
-  auto in = [&](const uint8_t* p, size_t rows) { return st.add(p, rows * count * 32); };
-  const size_t o_rs = in(b->responses, nr), o_x0 = in(b->C_x_0, 1), o_x1 = in(b->C_x_1, 1), o_cv = in(b->C_V, 1), o_cy = in(b->C_y, na),
-               o_av = b->attr_values ? in(b->attr_values, na) : st.reserve(0), o_cm = in(cm->main, n_main);
-  std::vector<std::array<size_t, 9>> eo(ne);
-  for (uint32_t e = 0; e < ne; e++) {
-    const afx_encproof_soa& q = b->enc[e];
-    const uint8_t* f[9] = { cm->enc[e], q.responses, q.pk, q.E1, q.E2, q.C_y_1, q.C_y_2, q.C_y_3, q.C_y_2p };   // (slot 0: the commitments in the challenge's place)
-    for (int i = 0; i < 9; i++) eo[e][i] = in(f[i], i == 0 ? 5 : i == 1 ? 6 : 1);
-  }
-  const size_t o_st = st.add(nullptr, count);
-  int rc = st.upload();
+  const size_t o_st = hc.res(status, 1, 1);
+  int rc = hc.st.upload();
   if (rc) return rc;
-  std::vector<afx_encproof_soa> de(ne);
-  std::vector<uint8_t*> dc(ne);
-  for (uint32_t e = 0; e < ne; e++) {
-    de[e] = { nullptr, st.dev(eo[e][1]), st.dev(eo[e][2]), st.dev(eo[e][3]), st.dev(eo[e][4]), st.dev(eo[e][5]), st.dev(eo[e][6]), st.dev(eo[e][7]), st.dev(eo[e][8]) };
-    dc[e] = st.dev(eo[e][0]);
-  }
-  const afx_presentation_soa d = { nullptr, st.dev(o_rs), st.dev(o_x0), st.dev(o_x1), st.dev(o_cv), st.dev(o_cy), b->attr_values ? st.dev(o_av) : nullptr, de.data() };
-  const afx_commitments_soa dcm = { st.dev(o_cm), dc.data() };
-  if ((rc = afx_verify_presentations_batchable_dev(ctx, shape, &d, &dcm, weights, count, st.dev(o_st)))) return rc;
-  AFX_HIP(hipMemcpyAsync(status, st.dev(o_st), count, hipMemcpyDeviceToHost, st.stream()));
-  AFX_HIP(hipStreamSynchronize(st.stream()));
-  return AFX_OK;
+  const std::vector<afx_encproof_soa> de = on_device(hc.st, oe);
+  std::vector<uint8_t*> dc(dm.proofs);
+  for (uint32_t e = 0; e < dm.proofs; e++) dc[e] = hc.st.dev(o_ce[e]);
+  afx_presentation_soa d = on_device(hc.st, om);
+  d.enc = de.data();
+  const afx_commitments_soa dcm = { hc.st.dev(o_cm), dc.data() };
+  if ((rc = afx_verify_presentations_batchable_dev(ctx, shape, &d, &dcm, weights, count, hc.st.dev(o_st)))) return rc;
+  return hc.fetch();
 } catch (...) { return afx::exception_rc(); }
 
 extern "C" int afx_verify_encryption_proofs_dev(afx_ctx* ctx, uint16_t index, const afx_encproof_soa* batch, size_t count, uint8_t* status_dev) try {
@@ -934,10 +911,7 @@ extern "C" int afx_verify_encryption_proofs_dev(afx_ctx* ctx, uint16_t index, co
   if (!ctx || !batch || !status_dev) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   if (count == 0) return AFX_OK;
   const afx_encproof_soa e = *batch;
-  if (index < ctx->n && (!e.challenge || !e.responses || !e.pk || !e.E1 || !e.E2 || !e.C_y_1 || !e.C_y_2 || !e.C_y_3 || !e.C_y_2p)) {
-    set_error("null batch array");
-    return AFX_E_BAD_ARGS;
-  }
+  if (index < ctx->n && any_null(e, Dims())) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
   return run_chunked(ctx, count, [&](Assembler& as, size_t off, uint32_t) {
     JobSets js;
     add_encproof_verify(as, js, index, e, count, off, 0);
@@ -948,16 +922,6 @@ extern "C" int afx_verify_encryption_proofs_dev(afx_ctx* ctx, uint16_t index, co
 // ------------------------------------------------------------------------------------------------
 // host-pointer front ends: stage the SoA batch into HBM, run the *_dev form, fetch the status bytes
 // ------------------------------------------------------------------------------------------------
-
-static void stage_encproof(Stager& st, const afx_encproof_soa& e, size_t total, size_t first, size_t n, size_t dn, size_t offs[9]) {
-  const uint8_t* f[9] = { e.challenge, e.responses, e.pk, e.E1, e.E2, e.C_y_1, e.C_y_2, e.C_y_3, e.C_y_2p };
-  for (int i = 0; i < 9; i++) offs[i] = st.add_rows(f[i], i == 1 ? 6 : 1, 32, total, first, n, dn);
-}
-static afx_encproof_soa dev_encproof(const Stager& st, const size_t offs[9]) {
-  afx_encproof_soa d = { st.dev(offs[0]), st.dev(offs[1]), st.dev(offs[2]), st.dev(offs[3]), st.dev(offs[4]),
-                         st.dev(offs[5]), st.dev(offs[6]), st.dev(offs[7]), st.dev(offs[8]) };
-  return d;
-}
 
 // Items [first, first + n) of a batch of `total` presentations held in host memory; `status` is the batch's status array
 // (element first + i answers item first + i), so that callers sharding one batch over several contexts share every array.
@@ -974,27 +938,26 @@ static int verify_presentations_host(afx_ctx* ctx, const afx_shape* shape, const
     int slot[AFX_MAX_ATTRIBUTES];
     if (presentation_shape_rejects(ctx, *shape, keep, &k, slot, pos)) { memset(status + first, AFX_ST_VERIFICATION_FAILURE, n); return AFX_OK; }
   }
-  const uint32_t na = shape->n_attributes, nr = shape->n_responses, ne = shape->n_enc_proofs;
-  if (!b->challenge || !b->C_x_0 || !b->C_x_1 || !b->C_V || (na && !b->C_y) || (nr && !b->responses) || (ne && !b->enc)) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
+  const Dims dm = dims_of(*shape);
+  if (any_null_with_proofs(*b, dm)) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
   // what makes two calls one pass (statements.hpp host_pipe): the statement, the shape's used fields, the mode, the optional array
   const afx_shape jsh = canonical_shape(*shape);
   const PlanKey jkey = plan_key("V", &jsh, sizeof jsh, mode_flags(ctx) | (b->attr_values ? (uint64_t)1 << 63 : 0));
   return host_pipe(ctx, n, [&](Stager& st, size_t off, size_t sn) -> int {
     const size_t f0 = first + off;
     const size_t dn = st.dev_items(sn);   // the pass's size on the device: small calls are padded to the size their plan is kept for
-    const size_t o_ch = st.add_rows(b->challenge, 1, 32, total, f0, sn, dn), o_rs = st.add_rows(b->responses, nr, 32, total, f0, sn, dn),
-                 o_x0 = st.add_rows(b->C_x_0, 1, 32, total, f0, sn, dn), o_x1 = st.add_rows(b->C_x_1, 1, 32, total, f0, sn, dn),
-                 o_cv = st.add_rows(b->C_V, 1, 32, total, f0, sn, dn), o_cy = st.add_rows(b->C_y, na, 32, total, f0, sn, dn),
-                 o_av = b->attr_values ? st.add_rows(b->attr_values, na, 32, total, f0, sn, dn) : st.reserve(0);
-    std::vector<std::array<size_t, 9>> eo(ne);
-    for (uint32_t e = 0; e < ne; e++) stage_encproof(st, b->enc[e], total, f0, sn, dn, eo[e].data());
+    // (attr_values is staged when the caller gives it, read or not; absent, an empty scratch stands in its place)
+    auto in = [&](const uint8_t* p, size_t rows, size_t elem) { return p ? st.add_rows(p, rows, elem, total, f0, sn, dn) : (st.reserve(0), NO_ARRAY); };
+    const Offsets<afx_presentation_soa> om = stage(*b, dm, in);
+    std::vector<Offsets<afx_encproof_soa>> oe(dm.proofs);
+    for (uint32_t e = 0; e < dm.proofs; e++) stage(oe[e], b->enc[e], dm, in);
     const size_t o_st = st.add(nullptr, dn);
     st.plan_fetch(status, o_st, 1, 1, total, f0, sn, dn);
     int rc = st.upload();
     if (rc) return rc;
-    std::vector<afx_encproof_soa> de(ne);
-    for (uint32_t e = 0; e < ne; e++) de[e] = dev_encproof(st, eo[e].data());
-    afx_presentation_soa d = { st.dev(o_ch), st.dev(o_rs), st.dev(o_x0), st.dev(o_x1), st.dev(o_cv), st.dev(o_cy), b->attr_values ? st.dev(o_av) : nullptr, de.data() };
+    const std::vector<afx_encproof_soa> de = on_device(st, oe);
+    afx_presentation_soa d = on_device(st, om);
+    d.enc = de.data();
     if ((rc = afx_verify_presentations_dev(ctx, shape, &d, dn, st.dev(o_st)))) return rc;
     return st.fetch_all();
   }, jkey);
@@ -1016,17 +979,18 @@ extern "C" int afx_verify_encryption_proofs(afx_ctx* ctx, uint16_t index, const 
   if (!ctx || !b || !status) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   if (count == 0) return AFX_OK;
   AFX_HIP(hipSetDevice(ctx->device));
-  Stager st(ctx);
-  size_t eo[9];
-  stage_encproof(st, *b, count, 0, count, count, eo);
-  const size_t o_st = st.add(nullptr, count);
-  int rc = st.upload();
+  // (index >= n: every item fails, no array is read - the device form answers)
+  if (index < ctx->n && any_null(*b, Dims())) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
+  HostCall hc(ctx, count, 0);
+  const Offsets<afx_encproof_soa> oe = stage(*b, Dims(), [&](const uint8_t* p, size_t rows, size_t elem) {
+    return p ? hc.st.add_rows(p, rows, elem, count, 0, count, count) : (hc.st.reserve(0), NO_ARRAY);
+  });
+  const size_t o_st = hc.res(status, 1, 1);
+  int rc = hc.st.upload();
   if (rc) return rc;
-  afx_encproof_soa d = dev_encproof(st, eo);
-  if ((rc = afx_verify_encryption_proofs_dev(ctx, index, &d, count, st.dev(o_st)))) return rc;
-  AFX_HIP(hipMemcpyAsync(status, st.dev(o_st), count, hipMemcpyDeviceToHost, ctx->stream));
-  AFX_HIP(hipStreamSynchronize(ctx->stream));
-  return AFX_OK;
+  const afx_encproof_soa d = on_device(hc.st, oe);
+  if ((rc = afx_verify_encryption_proofs_dev(ctx, index, &d, count, hc.st.dev(o_st)))) return rc;
+  return hc.fetch();
 } catch (...) { return afx::exception_rc(); }
 
 // ------------------------------------------------------------------------------------------------

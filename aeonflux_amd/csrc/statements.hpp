@@ -520,6 +520,27 @@ struct Stager {
   int launch_draws();
 };
 
+// A host-pointer call staged in one piece on lane 0 (the blind, tagged and batchable calls, afx_verify_encryption_proofs): inputs, results
+// and their fetch.  layout_tag: which family of front ends staged the arrays (Stager::layout_tag: blind and untagged calls 0, tagged 14).
+struct __attribute__((visibility("hidden"))) HostCall {   // (internal to the library: not among its exported symbols)
+  afx_ctx* ctx;
+  Stager st;
+  size_t count;
+  std::vector<std::pair<uint8_t*, std::pair<size_t, size_t>>> outs;   // host destination, (staged offset, bytes)
+  HostCall(afx_ctx* c, size_t n, uint32_t layout_tag) : ctx(c), st(c), count(n) { st.layout_tag = layout_tag; }
+  size_t in(const uint8_t* p, size_t rows, size_t elem = 32) { return (p && rows) ? st.add(p, rows * count * elem) : st.reserve(0); }
+  size_t res(uint8_t* dst, size_t rows, size_t elem = 32) {
+    const size_t off = st.add(nullptr, rows * count * elem);
+    if (dst && rows) outs.push_back({ dst, { off, rows * count * elem } });
+    return off;
+  }
+  int fetch() {
+    for (const auto& o : outs) AFX_HIP(hipMemcpyAsync(o.first, st.dev(o.second.first), o.second.second, hipMemcpyDeviceToHost, st.stream()));
+    AFX_HIP(hipStreamSynchronize(st.stream()));
+    return AFX_OK;
+  }
+};
+
 // The 40 bytes a device-drawn call stages (include/aeonflux_gpu.h afx_device_rng): seed || u64le(stream), the seed read from
 // getrandom(2) when the caller gives none.  Wiped when it goes out of scope.
 struct DrawSeed {

@@ -507,24 +507,6 @@ extern "C" int afx_unblind_issuances_dev(afx_ctx* ctx, const afx_attributes_soa*
 // answered here (its arrays' extents are the caller's own arithmetic on a layout the context does not have).
 // ------------------------------------------------------------------------------------------------
 namespace {
-struct HostCall {
-  afx_ctx* ctx;
-  Stager st;
-  size_t count;
-  std::vector<std::pair<uint8_t*, std::pair<size_t, size_t>>> outs;   // host destination, (staged offset, bytes)
-  HostCall(afx_ctx* c, size_t n) : ctx(c), st(c), count(n) {}
-  size_t in(const uint8_t* p, size_t rows, size_t elem = 32) { return (p && rows) ? st.add(p, rows * count * elem) : st.reserve(0); }
-  size_t res(uint8_t* dst, size_t rows, size_t elem = 32) {
-    const size_t off = st.add(nullptr, rows * count * elem);
-    if (dst && rows) outs.push_back({ dst, { off, rows * count * elem } });
-    return off;
-  }
-  int fetch() {
-    for (const auto& o : outs) AFX_HIP(hipMemcpyAsync(o.first, st.dev(o.second.first), o.second.second, hipMemcpyDeviceToHost, st.stream()));
-    AFX_HIP(hipStreamSynchronize(st.stream()));
-    return AFX_OK;
-  }
-};
 void zero_host(uint8_t* p, size_t rows, size_t count) { if (p && rows) memset(p, 0, rows * count * 32); }
 }  // namespace
 
@@ -545,7 +527,7 @@ extern "C" int afx_blind_request(afx_ctx* ctx, const afx_attributes_soa* attrs, 
     return AFX_E_BAD_ARGS;
   }
   AFX_HIP(hipSetDevice(ctx->device));
-  HostCall hc(ctx, count);
+  HostCall hc(ctx, count, 0);
   const size_t o_val = hc.in(attrs->values, L.n), o_d = hc.in(d, 1), o_rw = hc.in(rnd->r_wide, L.h, 64), o_seed = hc.in(rnd->rng_seed, 1);
   const size_t o_D = hc.res(out->D, 1), o_A = hc.res(out->A, L.h), o_B = hc.res(out->B, L.h), o_ch = hc.res(out->challenge, 1),
                o_rs = hc.res(out->responses, L.request_responses()), o_st = hc.res(status, 1, 1);
@@ -569,7 +551,7 @@ extern "C" int afx_verify_blind_requests(afx_ctx* ctx, const afx_attributes_soa*
   const afx_blind_request_soa& q = *requests;
   if (!q.D || !q.challenge || !q.responses || (L.h && (!q.A || !q.B))) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
   AFX_HIP(hipSetDevice(ctx->device));
-  HostCall hc(ctx, count);
+  HostCall hc(ctx, count, 0);
   const size_t o_D = hc.in(q.D, 1), o_A = hc.in(q.A, L.h), o_B = hc.in(q.B, L.h), o_ch = hc.in(q.challenge, 1), o_rs = hc.in(q.responses, n_responses),
                o_st = hc.res(status, 1, 1);
   int rc = hc.st.upload();
@@ -602,7 +584,7 @@ extern "C" int afx_issue_blind(afx_ctx* ctx, const afx_attributes_soa* attrs, co
   }
   AFX_HIP(hipSetDevice(ctx->device));
   const uint32_t nr = ctx->n + 6;
-  HostCall hc(ctx, count);
+  HostCall hc(ctx, count, 0);
   // the rows of hidden positions stay on the host: the issuer's plan never reads them (zeros stand in their place)
   std::vector<size_t> o_val(L.n);
   const size_t val_block = hc.st.reserve((size_t)L.n * count * 32);
@@ -638,7 +620,7 @@ extern "C" int afx_unblind_issuances(afx_ctx* ctx, const afx_attributes_soa* att
     return AFX_E_BAD_ARGS;
   }
   AFX_HIP(hipSetDevice(ctx->device));
-  HostCall hc(ctx, count);
+  HostCall hc(ctx, count, 0);
   const size_t o_val = hc.in(attrs->values, L.n), o_d = hc.in(d, 1), o_D = hc.in(q.D, 1), o_A = hc.in(q.A, L.h), o_B = hc.in(q.B, L.h), o_t = hc.in(s.t, 1),
                o_U = hc.in(s.U, 1), o_S1 = hc.in(s.S1, 1), o_S2 = hc.in(s.S2, 1), o_ch = hc.in(s.challenge, 1), o_rs = hc.in(s.responses, n_responses);
   const size_t r_V = hc.res(V, 1), o_st = hc.res(status, 1, 1);

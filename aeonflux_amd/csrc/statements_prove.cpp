@@ -8,6 +8,7 @@
 //                                           + Keypair::encrypt (src/symmetric.rs:252-261)
 //   /root/reference/src/parameters.rs:349-362, src/amacs.rs:104  IssuerParameters::generate, W = w*G_w
 #include "statements.hpp"
+#include "batch_arrays.hpp"
 
 static bool is_scalar_kind(uint8_t k) { return k == AFX_ATTR_PUBLIC_SCALAR || k == AFX_ATTR_SECRET_SCALAR; }
 
@@ -285,15 +286,8 @@ int show_dev_impl(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keyp
   if (nsp && (!cr.M2 || !cr.m3 || !out->enc)) { set_error("hidden group elements need M2, m3 and enc outputs"); return AFX_E_BAD_ARGS; }
   const bool no_key = nsp && !keypairs;   // CredentialError::NoSymmetricKey (:150-157)
   if (!no_key) {
-    bool missing = !cr.values || !cr.t || !cr.U || !cr.V || !rnd->z_wide || !rnd->rng_seed || !out->challenge || !out->responses || !out->C_x_0 ||
-                   !out->C_x_1 || !out->C_V || !out->C_y;
-    if (nsp) {
-      missing |= !rnd->enc_seeds || !keypairs->a || !keypairs->a0 || !keypairs->a1 || !keypairs->pk;
-      for (uint32_t e = 0; e < nsp; e++) {
-        const afx_encproof_out& q = out->enc[e];
-        missing |= !q.challenge || !q.responses || !q.pk || !q.E1 || !q.E2 || !q.C_y_1 || !q.C_y_2 || !q.C_y_3 || !q.C_y_2p;
-      }
-    }
+    const Dims dm = dims_of(cr);   // (M2, m3 and out->enc were looked at above)
+    bool missing = any_null(cr, dm) || any_null(*rnd, dm) || any_null_with_proofs(*out, outputs(dm)) || (nsp && any_null(*keypairs, dm));
     if (tag) missing |= !tag->H_rows || !tag->nonce || !tag->inv || !tag->seed || !tag->T || !tag->challenge || !tag->responses;
     if (missing) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
   }
@@ -320,16 +314,11 @@ int show_dev_impl(afx_ctx* ctx, const afx_credentials_soa* creds, const afx_keyp
     // a tagged show: every output row of the call, for the masking in front of k_finish
     std::vector<uint8_t*> tag_outs;
     if (tag) {
-      auto rows_of = [&](uint8_t* base, size_t rows) { for (size_t k = 0; base && k < rows; k++) tag_outs.push_back(orow(base, k)); };
-      rows_of(o.challenge, 1); rows_of(o.responses, 3 + hs); rows_of(o.C_x_0, 1); rows_of(o.C_x_1, 1); rows_of(o.C_V, 1); rows_of(o.C_y, na);
-      for (uint32_t i = 0; i < na; i++)
-        if (cr.kinds[i] != AFX_ATTR_SECRET_SCALAR && cr.kinds[i] != AFX_ATTR_SECRET_POINT && o.attr_values) tag_outs.push_back(orow(o.attr_values, i));
-      for (uint32_t e = 0; e < nsp; e++) {
-        const afx_encproof_out& q = eo[e];
-        rows_of(q.challenge, 1); rows_of(q.responses, 6);
-        for (uint8_t* p : { q.pk, q.E1, q.E2, q.C_y_1, q.C_y_2, q.C_y_3, q.C_y_2p }) rows_of(p, 1);
-      }
-      rows_of(tag->T, 1); rows_of(tag->challenge, 1); rows_of(tag->responses, 2);
+      const Dims dm = dims_of(cr);
+      auto cell = [&](uint8_t* base, uint32_t k) { tag_outs.push_back(orow(base, k)); };
+      each_cell(o, dm, cell);
+      for (uint32_t e = 0; e < nsp; e++) each_cell(eo[e], dm, cell);
+      each_cell(afx_tags_out{ tag->T, tag->challenge, tag->responses }, dm, cell);
     }
     if (no_key) {
       as.fail_all = true;
@@ -696,14 +685,12 @@ static int show_range_impl(afx_ctx* ctx, const afx_credentials_soa* creds, const
   if (!ctx || !creds || !rnd || !out || !shape_out || !status) { set_error("null argument"); return AFX_E_BAD_ARGS; }
   const uint32_t na = creds->n_attributes;
   if (na == 0 || na > ctx->n) { set_error("credential attribute count does not fit the system parameters"); return AFX_E_BAD_ARGS; }
-  uint32_t hs = 0, nsp = 0;
-  for (uint32_t i = 0; i < na; i++) { hs += creds->kinds[i] == AFX_ATTR_SECRET_SCALAR; nsp += creds->kinds[i] == AFX_ATTR_SECRET_POINT; }
-  if (!creds->values || !creds->t || !creds->U || !creds->V || !rnd->z_wide || !rnd->rng_seed || !out->challenge || !out->responses ||
-      !out->C_x_0 || !out->C_x_1 || !out->C_V || !out->C_y || (nsp && (!rnd->enc_seeds || !out->enc || !creds->M2 || !creds->m3))) {
-    set_error("null batch array");
-    return AFX_E_BAD_ARGS;
-  }
-  if (keypairs && nsp && (!keypairs->a || !keypairs->a0 || !keypairs->a1 || !keypairs->pk)) { set_error("null keypair array"); return AFX_E_BAD_ARGS; }
+  const Dims dm = dims_of(*creds);
+  const uint32_t nsp = dm.proofs;
+  if (any_null(*creds, dm) || any_null(*rnd, dm) || any_null(*out, outputs(dm)) || (nsp && !out->enc)) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
+  if (keypairs && nsp && any_null(*keypairs, dm)) { set_error("null keypair array"); return AFX_E_BAD_ARGS; }
+  // (a proof's own output arrays, as afx_show_tagged asks: staged, a null one would be computed and dropped)
+  if (any_null_with_proofs(*out, outputs(dm))) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
   if (first > total || n > total - first) { set_error("range outside the batch"); return AFX_E_BAD_ARGS; }
   AFX_HIP(hipSetDevice(ctx->device));
   const bool kp = keypairs && nsp;
@@ -733,25 +720,20 @@ static int show_range_impl(afx_ctx* ctx, const afx_credentials_soa* creds, const
   return host_pipe(ctx, n, [&](Stager& st, size_t off, size_t sn) -> int {
     const size_t f0 = first + off;
     const size_t dn = st.dev_items(sn);
-    auto in = [&](const uint8_t* p, size_t rows, size_t elem) { return (p && rows) ? st.add_rows(p, rows, elem, total, f0, sn, dn) : st.reserve(0); };
+    auto in = [&](const uint8_t* p, size_t rows, size_t elem) { return (p && rows) ? st.add_rows(p, rows, elem, total, f0, sn, dn) : (st.reserve(0), NO_ARRAY); };
     auto res = [&](uint8_t* dst, size_t rows, size_t elem) {
       const size_t o = st.add(nullptr, rows * dn * elem);
       st.plan_fetch(dst, o, rows, elem, total, f0, sn, dn);
       return o;
     };
-    const size_t o_val = in(creds->values, na, 32), o_M2 = in(nsp ? creds->M2 : nullptr, nsp ? na : 0, 32), o_m3 = in(nsp ? creds->m3 : nullptr, nsp ? na : 0, 32),
-                 o_t = in(creds->t, 1, 32), o_U = in(creds->U, 1, 32), o_V = in(creds->V, 1, 32), o_zw = in(rnd->z_wide, 1, 64),
-                 o_seed = in(rnd->rng_seed, 1, 32), o_es = in(nsp ? rnd->enc_seeds : nullptr, nsp, 32);
-    size_t o_kp[4] = { 0, 0, 0, 0 };
-    if (kp) { o_kp[0] = in(keypairs->a, 1, 32); o_kp[1] = in(keypairs->a0, 1, 32); o_kp[2] = in(keypairs->a1, 1, 32); o_kp[3] = in(keypairs->pk, 1, 32); }
-    const size_t o_ch = res(out->challenge, 1, 32), o_rs = res(out->responses, 3 + hs, 32), o_x0 = res(out->C_x_0, 1, 32), o_x1 = res(out->C_x_1, 1, 32),
-                 o_cv = res(out->C_V, 1, 32), o_cy = res(out->C_y, na, 32), o_av = res(out->attr_values, na, 32), o_st = res(status, 1, 1);
-    std::vector<std::array<size_t, 9>> oe(nsp);
-    for (uint32_t e = 0; e < nsp; e++) {
-      uint8_t* dst[9] = { out->enc[e].challenge, out->enc[e].responses, out->enc[e].pk, out->enc[e].E1, out->enc[e].E2,
-                          out->enc[e].C_y_1, out->enc[e].C_y_2, out->enc[e].C_y_3, out->enc[e].C_y_2p };
-      for (int f = 0; f < 9; f++) oe[e][f] = res(dst[f], f == 1 ? 6 : 1, 32);
-    }
+    const Offsets<afx_credentials_soa> oc = stage(*creds, dm, in);
+    const Offsets<afx_show_randomness> orn = stage(*rnd, dm, in);
+    Offsets<afx_keypairs_soa> ok;
+    if (kp) stage(ok, *keypairs, dm, in);
+    const Offsets<afx_presentation_out> om = stage(*out, dm, res);   // (attr_values: its rows are written whether or not the caller takes them)
+    const size_t o_st = res(status, 1, 1);
+    std::vector<Offsets<afx_encproof_out>> oe(nsp);
+    for (uint32_t e = 0; e < nsp; e++) stage(oe[e], out->enc[e], dm, res);
     size_t o_cm = 0;
     std::vector<size_t> o_ce(nsp);
     if (cm) {
@@ -760,15 +742,12 @@ static int show_range_impl(afx_ctx* ctx, const afx_credentials_soa* creds, const
     }
     int rc = st.upload();
     if (rc) return rc;
-    afx_credentials_soa dc = *creds;
-    dc.values = st.dev(o_val); dc.M2 = nsp ? st.dev(o_M2) : nullptr; dc.m3 = nsp ? st.dev(o_m3) : nullptr;
-    dc.t = st.dev(o_t); dc.U = st.dev(o_U); dc.V = st.dev(o_V);
-    afx_keypairs_soa dk = { st.dev(o_kp[0]), st.dev(o_kp[1]), st.dev(o_kp[2]), st.dev(o_kp[3]) };
-    afx_show_randomness dr = { st.dev(o_zw), st.dev(o_seed), st.dev(o_es) };
-    std::vector<afx_encproof_out> de(nsp);
-    for (uint32_t e = 0; e < nsp; e++)
-      de[e] = { st.dev(oe[e][0]), st.dev(oe[e][1]), st.dev(oe[e][2]), st.dev(oe[e][3]), st.dev(oe[e][4]), st.dev(oe[e][5]), st.dev(oe[e][6]), st.dev(oe[e][7]), st.dev(oe[e][8]) };
-    afx_presentation_out dout = { st.dev(o_ch), st.dev(o_rs), st.dev(o_x0), st.dev(o_x1), st.dev(o_cv), st.dev(o_cy), st.dev(o_av), de.data() };
+    const afx_credentials_soa dc = on_device(st, oc, *creds);
+    const afx_keypairs_soa dk = on_device(st, ok);
+    const afx_show_randomness dr = on_device(st, orn);
+    const std::vector<afx_encproof_out> de = on_device(st, oe);
+    afx_presentation_out dout = on_device(st, om);
+    dout.enc = de.data();
     std::vector<uint8_t*> dce(nsp);
     for (uint32_t e = 0; cm && e < nsp; e++) dce[e] = st.dev(o_ce[e]);
     const afx_commitments_soa dcm = { cm ? st.dev(o_cm) : nullptr, dce.data() };

@@ -10,6 +10,7 @@
 // Where the cells and rows lie: a _dev call's in the lane's tag buffer; a host-pointer call's in scratch of its own staging, so that
 // its plan names only addresses the relocation knows and small calls keep their plans (run_chunked keeps no plan of a _dev call).
 #include "statements.hpp"
+#include "batch_arrays.hpp"
 
 namespace {
 // H -> the lane's buffer; H_rows[i] = H for i < count; inv[i] = (m[i] + n[i])^-1 when m_dev is given.  Refuses an H that is the identity
@@ -82,26 +83,6 @@ int tag_rows(afx_ctx* ctx, const uint8_t* H, const uint8_t* m_dev, const uint8_t
   return AFX_OK;
 }
 
-// a host-pointer call staged in one piece (as the blind and batchable calls are)
-struct HostCall {
-  afx_ctx* ctx;
-  Stager st;
-  size_t count;
-  std::vector<std::pair<uint8_t*, std::pair<size_t, size_t>>> outs;   // host destination, (staged offset, bytes)
-  HostCall(afx_ctx* c, size_t n) : ctx(c), st(c), count(n) { st.layout_tag = 14; }   // (part of the plan-cache key: a staging layout of its own)
-  size_t in(const uint8_t* p, size_t rows, size_t elem = 32) { return (p && rows) ? st.add(p, rows * count * elem) : st.reserve(0); }
-  size_t res(uint8_t* dst, size_t rows, size_t elem = 32) {
-    const size_t off = st.add(nullptr, rows * count * elem);
-    if (dst && rows) outs.push_back({ dst, { off, rows * count * elem } });
-    return off;
-  }
-  int fetch() {
-    for (const auto& o : outs) AFX_HIP(hipMemcpyAsync(o.first, st.dev(o.second.first), o.second.second, hipMemcpyDeviceToHost, st.stream()));
-    AFX_HIP(hipStreamSynchronize(st.stream()));
-    return AFX_OK;
-  }
-};
-bool tags_in_missing(const afx_tags_soa* t) { return !t->nonce || !t->T || !t->challenge || !t->responses; }
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -134,7 +115,7 @@ static int show_tagged_dev_impl(afx_ctx* ctx, const afx_credentials_soa* creds, 
     set_error("a tag needs the position of a hidden scalar attribute");
     return AFX_E_BAD_ARGS;
   }
-  if (!creds->values || !nonce || !tag_seed || !tags_out->T || !tags_out->challenge || !tags_out->responses) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
+  if (!creds->values || !nonce || !tag_seed || any_null(*tags_out, Dims())) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
   hipStream_t stream = nullptr;
   int rc = tag_rows(ctx, tag->scope_generator, creds->values + (size_t)ts.position * count * 32, nonce, count, H_dst, inv_dst, &ts.H_rows, &ts.inv, &stream);
   if (rc) return rc;
@@ -162,50 +143,39 @@ extern "C" int afx_show_tagged(afx_ctx* ctx, const afx_credentials_soa* creds, c
   if (count == 0) return afx_show_tagged_dev(ctx, creds, keypairs, rnd, tag, nonce, tag_seed, 0, out, tags_out, shape_out, status);
   const uint32_t na = creds->n_attributes;
   if (na == 0 || na > ctx->n) { set_error("credential attribute count does not fit the system parameters"); return AFX_E_BAD_ARGS; }
-  uint32_t hs = 0, nsp = 0;
-  for (uint32_t i = 0; i < na; i++) { hs += creds->kinds[i] == AFX_ATTR_SECRET_SCALAR; nsp += creds->kinds[i] == AFX_ATTR_SECRET_POINT; }
-  if (!creds->values || !creds->t || !creds->U || !creds->V || !rnd->z_wide || !rnd->rng_seed || !out->challenge || !out->responses || !out->C_x_0 || !out->C_x_1 ||
-      !out->C_V || !out->C_y || (nsp && (!rnd->enc_seeds || !out->enc || !creds->M2 || !creds->m3)) || !nonce || !tag_seed || !tags_out->T || !tags_out->challenge ||
-      !tags_out->responses) {
+  const Dims dm = dims_of(*creds);
+  if (any_null(*creds, dm) || any_null(*rnd, dm) || any_null(*out, outputs(dm)) || (dm.proofs && !out->enc) || !nonce || !tag_seed || any_null(*tags_out, dm)) {
     set_error("null batch array");
     return AFX_E_BAD_ARGS;
   }
-  const bool kp = keypairs && nsp;
-  if (kp && (!keypairs->a || !keypairs->a0 || !keypairs->a1 || !keypairs->pk)) { set_error("null keypair array"); return AFX_E_BAD_ARGS; }
-  for (uint32_t e = 0; e < nsp; e++) {
-    const afx_encproof_out& q = out->enc[e];
-    if (!q.challenge || !q.responses || !q.pk || !q.E1 || !q.E2 || !q.C_y_1 || !q.C_y_2 || !q.C_y_3 || !q.C_y_2p) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
-  }
+  const bool kp = keypairs && dm.proofs;
+  if (kp && any_null(*keypairs, dm)) { set_error("null keypair array"); return AFX_E_BAD_ARGS; }
+  if (any_null_with_proofs(*out, outputs(dm))) { set_error("null batch array"); return AFX_E_BAD_ARGS; }   // (the proofs' arrays)
   AFX_HIP(hipSetDevice(ctx->device));
-  HostCall hc(ctx, count);
-  const size_t o_val = hc.in(creds->values, na), o_M2 = hc.in(nsp ? creds->M2 : nullptr, na), o_m3 = hc.in(nsp ? creds->m3 : nullptr, na), o_t = hc.in(creds->t, 1),
-               o_U = hc.in(creds->U, 1), o_V = hc.in(creds->V, 1), o_zw = hc.in(rnd->z_wide, 1, 64), o_seed = hc.in(rnd->rng_seed, 1),
-               o_es = hc.in(nsp ? rnd->enc_seeds : nullptr, nsp), o_n = hc.in(nonce, 1), o_ts = hc.in(tag_seed, 1);
-  size_t o_kp[4] = { 0, 0, 0, 0 };
-  if (kp) { o_kp[0] = hc.in(keypairs->a, 1); o_kp[1] = hc.in(keypairs->a0, 1); o_kp[2] = hc.in(keypairs->a1, 1); o_kp[3] = hc.in(keypairs->pk, 1); }
-  const size_t o_ch = hc.res(out->challenge, 1), o_rs = hc.res(out->responses, 3 + hs), o_x0 = hc.res(out->C_x_0, 1), o_x1 = hc.res(out->C_x_1, 1),
-               o_cv = hc.res(out->C_V, 1), o_cy = hc.res(out->C_y, na), o_av = hc.res(out->attr_values, out->attr_values ? na : 0),
-               o_T = hc.res(tags_out->T, 1), o_tc = hc.res(tags_out->challenge, 1), o_tr = hc.res(tags_out->responses, 2), o_st = hc.res(status, 1, 1);
-  std::vector<std::array<size_t, 9>> oe(nsp);
-  for (uint32_t e = 0; e < nsp; e++) {
-    uint8_t* dst[9] = { out->enc[e].challenge, out->enc[e].responses, out->enc[e].pk, out->enc[e].E1, out->enc[e].E2,
-                        out->enc[e].C_y_1, out->enc[e].C_y_2, out->enc[e].C_y_3, out->enc[e].C_y_2p };
-    for (int f = 0; f < 9; f++) oe[e][f] = hc.res(dst[f], f == 1 ? 6 : 1);
-  }
+  HostCall hc(ctx, count, 14);   // (a staging layout of its own: part of the plan-cache key)
+  auto in = [&](const uint8_t* p, size_t rows, size_t elem) { const size_t o = hc.in(p, rows, elem); return p ? o : NO_ARRAY; };
+  auto res = [&](uint8_t* dst, size_t rows, size_t elem) { const size_t o = hc.res(dst, dst ? rows : 0, elem); return dst ? o : NO_ARRAY; };   // (attr_values may be absent)
+  const Offsets<afx_credentials_soa> oc = stage(*creds, dm, in);
+  const Offsets<afx_show_randomness> orn = stage(*rnd, dm, in);
+  const size_t o_n = hc.in(nonce, 1), o_ts = hc.in(tag_seed, 1);
+  Offsets<afx_keypairs_soa> ok;
+  if (kp) stage(ok, *keypairs, dm, in);
+  const Offsets<afx_presentation_out> om = stage(*out, dm, res);
+  const Offsets<afx_tags_out> ot = stage(*tags_out, dm, res);
+  const size_t o_st = hc.res(status, 1, 1);
+  std::vector<Offsets<afx_encproof_out>> oe(dm.proofs);
+  for (uint32_t e = 0; e < dm.proofs; e++) stage(oe[e], out->enc[e], dm, res);
   const size_t o_H = hc.st.reserve(32 * count), o_inv = hc.st.reserve(32 * count);   // the cells of H, the inverse rows
   int rc = hc.st.upload();
   if (rc) return rc;
   Stager& st = hc.st;
-  afx_credentials_soa dc = *creds;
-  dc.values = st.dev(o_val); dc.M2 = nsp ? st.dev(o_M2) : nullptr; dc.m3 = nsp ? st.dev(o_m3) : nullptr;
-  dc.t = st.dev(o_t); dc.U = st.dev(o_U); dc.V = st.dev(o_V);
-  const afx_keypairs_soa dk = { st.dev(o_kp[0]), st.dev(o_kp[1]), st.dev(o_kp[2]), st.dev(o_kp[3]) };
-  const afx_show_randomness dr = { st.dev(o_zw), st.dev(o_seed), st.dev(o_es) };
-  std::vector<afx_encproof_out> de(nsp);
-  for (uint32_t e = 0; e < nsp; e++)
-    de[e] = { st.dev(oe[e][0]), st.dev(oe[e][1]), st.dev(oe[e][2]), st.dev(oe[e][3]), st.dev(oe[e][4]), st.dev(oe[e][5]), st.dev(oe[e][6]), st.dev(oe[e][7]), st.dev(oe[e][8]) };
-  const afx_presentation_out dout = { st.dev(o_ch), st.dev(o_rs), st.dev(o_x0), st.dev(o_x1), st.dev(o_cv), st.dev(o_cy), out->attr_values ? st.dev(o_av) : nullptr, de.data() };
-  const afx_tags_out dto = { st.dev(o_T), st.dev(o_tc), st.dev(o_tr) };
+  const afx_credentials_soa dc = on_device(st, oc, *creds);
+  const afx_keypairs_soa dk = on_device(st, ok);
+  const afx_show_randomness dr = on_device(st, orn);
+  const std::vector<afx_encproof_out> de = on_device(st, oe);
+  afx_presentation_out dout = on_device(st, om);
+  dout.enc = de.data();
+  const afx_tags_out dto = on_device(st, ot);
   if ((rc = show_tagged_dev_impl(ctx, &dc, kp ? &dk : nullptr, &dr, tag, st.dev(o_n), st.dev(o_ts), count, &dout, &dto, shape_out, st.dev(o_st), st.dev(o_H), st.dev(o_inv))))
     return rc;
   return hc.fetch();
@@ -224,7 +194,7 @@ static int verify_presentations_tagged_dev_impl(afx_ctx* ctx, const afx_shape* s
   memset(&tv, 0, sizeof tv);
   tv.position = tag->position;
   if (tagged_shape_ok(ctx, *shape, tv.position)) {   // (otherwise every item fails and no tag array is read)
-    if (tags_in_missing(tags)) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
+    if (any_null(*tags, Dims())) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
     tv.nonce = tags->nonce; tv.T = tags->T; tv.challenge = tags->challenge; tv.responses = tags->responses;
   }
   const int rc = tag_rows(ctx, tag->scope_generator, nullptr, nullptr, count, H_dst, nullptr, &tv.H_rows, nullptr);
@@ -245,7 +215,7 @@ static int verify_tag_proofs_dev_impl2(afx_ctx* ctx, const afx_tag_statement* ta
   memset(&tv, 0, sizeof tv);
   tv.position = tag->position;
   if (tv.position < ctx->n) {
-    if (!C_y_p || tags_in_missing(tags)) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
+    if (!C_y_p || any_null(*tags, Dims())) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
     tv.nonce = tags->nonce; tv.T = tags->T; tv.challenge = tags->challenge; tv.responses = tags->responses;
   }
   const int rc = tag_rows(ctx, tag->scope_generator, nullptr, nullptr, count, H_dst, nullptr, &tv.H_rows, nullptr);
@@ -269,8 +239,8 @@ extern "C" int afx_verify_tag_proofs(afx_ctx* ctx, const afx_tag_statement* tag,
     memset(status, AFX_ST_VERIFICATION_FAILURE, count);
     return AFX_OK;
   }
-  if (!C_y_p || tags_in_missing(tags)) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
-  HostCall hc(ctx, count);
+  if (!C_y_p || any_null(*tags, Dims())) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
+  HostCall hc(ctx, count, 14);   // (a staging layout of its own: part of the plan-cache key)
   const size_t o_cy = hc.in(C_y_p, 1), o_n = hc.in(tags->nonce, 1), o_T = hc.in(tags->T, 1), o_ch = hc.in(tags->challenge, 1), o_rs = hc.in(tags->responses, 2),
                o_st = hc.res(status, 1, 1);
   const size_t o_H = hc.st.reserve(32 * count);   // the cells of H
@@ -297,35 +267,23 @@ extern "C" int afx_verify_presentations_tagged(afx_ctx* ctx, const afx_shape* sh
     memset(status, AFX_ST_VERIFICATION_FAILURE, count);
     return AFX_OK;
   }
-  const uint32_t na = shape->n_attributes, nr = shape->n_responses, ne = shape->n_enc_proofs;
-  bool missing = !b->challenge || !b->C_x_0 || !b->C_x_1 || !b->C_V || (na && !b->C_y) || (nr && !b->responses) || (ne && !b->enc) || tags_in_missing(tags);
-  for (uint32_t i = 0; i < na; i++)
-    if ((shape->kinds[i] == AFX_ENC_PUBLIC_SCALAR || shape->kinds[i] == AFX_ENC_PUBLIC_POINT) && !b->attr_values) missing = true;
-  for (uint32_t e = 0; e < ne && !missing; e++) {
-    const afx_encproof_soa& q = b->enc[e];
-    missing |= !q.challenge || !q.responses || !q.pk || !q.E1 || !q.E2 || !q.C_y_1 || !q.C_y_2 || !q.C_y_3 || !q.C_y_2p;
-  }
-  if (missing) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
-  HostCall hc(ctx, count);
-  const size_t o_ch = hc.in(b->challenge, 1), o_rs = hc.in(b->responses, nr), o_x0 = hc.in(b->C_x_0, 1), o_x1 = hc.in(b->C_x_1, 1), o_cv = hc.in(b->C_V, 1),
-               o_cy = hc.in(b->C_y, na), o_av = hc.in(b->attr_values, na), o_n = hc.in(tags->nonce, 1), o_T = hc.in(tags->T, 1), o_tc = hc.in(tags->challenge, 1),
-               o_tr = hc.in(tags->responses, 2);
-  std::vector<std::array<size_t, 9>> eo(ne);
-  for (uint32_t e = 0; e < ne; e++) {
-    const afx_encproof_soa& q = b->enc[e];
-    const uint8_t* f[9] = { q.challenge, q.responses, q.pk, q.E1, q.E2, q.C_y_1, q.C_y_2, q.C_y_3, q.C_y_2p };
-    for (int i = 0; i < 9; i++) eo[e][i] = hc.in(f[i], i == 1 ? 6 : 1);
-  }
+  const Dims dm = dims_of(*shape);
+  if (any_null_with_proofs(*b, dm) || any_null(*tags, dm)) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
+  HostCall hc(ctx, count, 14);   // (a staging layout of its own: part of the plan-cache key)
+  auto in = [&](const uint8_t* p, size_t rows, size_t elem) { const size_t o = hc.in(p, rows, elem); return p ? o : NO_ARRAY; };
+  const Offsets<afx_presentation_soa> om = stage(*b, dm, in);
+  const Offsets<afx_tags_soa> ot = stage(*tags, dm, in);
+  std::vector<Offsets<afx_encproof_soa>> oe(dm.proofs);
+  for (uint32_t e = 0; e < dm.proofs; e++) stage(oe[e], b->enc[e], dm, in);
   const size_t o_st = hc.res(status, 1, 1);
   const size_t o_H = hc.st.reserve(32 * count);   // the cells of H
   int rc = hc.st.upload();
   if (rc) return rc;
   Stager& st = hc.st;
-  std::vector<afx_encproof_soa> de(ne);
-  for (uint32_t e = 0; e < ne; e++)
-    de[e] = { st.dev(eo[e][0]), st.dev(eo[e][1]), st.dev(eo[e][2]), st.dev(eo[e][3]), st.dev(eo[e][4]), st.dev(eo[e][5]), st.dev(eo[e][6]), st.dev(eo[e][7]), st.dev(eo[e][8]) };
-  const afx_presentation_soa d = { st.dev(o_ch), st.dev(o_rs), st.dev(o_x0), st.dev(o_x1), st.dev(o_cv), st.dev(o_cy), b->attr_values ? st.dev(o_av) : nullptr, de.data() };
-  const afx_tags_soa dt = { st.dev(o_n), st.dev(o_T), st.dev(o_tc), st.dev(o_tr) };
+  const std::vector<afx_encproof_soa> de = on_device(st, oe);
+  afx_presentation_soa d = on_device(st, om);
+  d.enc = de.data();
+  const afx_tags_soa dt = on_device(st, ot);
   if ((rc = verify_presentations_tagged_dev_impl(ctx, shape, &d, tag, &dt, count, st.dev(o_st), st.dev(o_H)))) return rc;
   return hc.fetch();
 } catch (...) { return afx::exception_rc(); }

@@ -7,6 +7,7 @@
 #include <string.h>
 #include "wire_formats.hpp"
 #include "records.hpp"
+#include "batch_arrays.hpp"
 
 // ---- Presentation batches ("AFXP" v1) ------------------------------------------------------------
 extern "C" uint32_t afx_wire_cells_per_record(const afx_shape* sh) { return sh && shape_ok(*sh) ? presentation_cells(*sh, 1, 14) : 0; }
@@ -39,25 +40,15 @@ extern "C" int afx_wire_pack_presentations(const afx_shape* shape, const afx_pre
   if (blob_cap < len) { set_error("blob buffer too small"); return AFX_E_BAD_ARGS; }
   const afx_shape& sh = *shape;
   const afx_presentation_soa& b = *batch;
-  bool missing = count && (!b.challenge || !b.C_x_0 || !b.C_x_1 || !b.C_V || (sh.n_attributes && !b.C_y) || (sh.n_responses && !b.responses) || (sh.n_enc_proofs && !b.enc));
-  for (uint32_t i = 0; i < sh.n_attributes; i++)
-    if (revealed(sh.kinds[i]) && count && !b.attr_values) missing = true;
-  for (uint32_t e = 0; e < sh.n_enc_proofs && !missing && count; e++) {
-    const afx_encproof_soa& q = b.enc[e];
-    missing |= !q.challenge || !q.responses || !q.pk || !q.E1 || !q.E2 || !q.C_y_1 || !q.C_y_2 || !q.C_y_3 || !q.C_y_2p;
-  }
-  if (missing) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
+  const Dims dm = dims_of(sh);
+  if (count && any_null_with_proofs(b, dm)) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
   write_header(FORMATS[AFXP], blob, sh, count, cells);
+  if (!count) return AFX_OK;   // (no record: no array is looked at)
   // the record's cells, in order: where each comes from in the struct-of-arrays ([row][count][32])
   std::vector<const uint8_t*> col;
-  auto rows = [&](const uint8_t* base, uint32_t k) { for (uint32_t r = 0; r < k; r++) col.push_back(base + (size_t)r * count * 32); };
-  rows(b.challenge, 1); rows(b.responses, sh.n_responses); rows(b.C_x_0, 1); rows(b.C_x_1, 1); rows(b.C_V, 1); rows(b.C_y, sh.n_attributes);
-  for (uint32_t i = 0; i < sh.n_attributes; i++)
-    if (revealed(sh.kinds[i])) col.push_back(b.attr_values + (size_t)i * count * 32);
-  for (uint32_t e = 0; e < sh.n_enc_proofs; e++) {
-    const afx_encproof_soa& q = b.enc[e];
-    rows(q.challenge, 1); rows(q.responses, 6); rows(q.pk, 1); rows(q.E1, 1); rows(q.E2, 1); rows(q.C_y_1, 1); rows(q.C_y_2, 1); rows(q.C_y_3, 1); rows(q.C_y_2p, 1);
-  }
+  auto cell = [&](const uint8_t* base, uint32_t r) { col.push_back(base + (size_t)r * count * 32); };
+  each_cell(b, dm, cell);
+  for (uint32_t e = 0; e < sh.n_enc_proofs; e++) each_cell(b.enc[e], dm, cell);
   if (col.size() != cells) { set_error("internal: wire cell list"); return AFX_E_BAD_ARGS; }
   uint8_t* rec = blob + hdr;
   for (size_t i = 0; i < count; i++)
@@ -91,17 +82,11 @@ static int verify_wire_records(afx_ctx* ctx, const afx_shape& sh, const uint8_t*
     if (rc2) return rc2;
     if ((rc2 = transpose_in(st, o_rec, o_soa, o_map, cells, dn))) return rc2;
     auto rowp = [&](uint32_t r) { return (const uint8_t*)st.dev(o_soa) + (size_t)r * dn * 32; };
+    const Dims dm = dims_of(sh);
     afx_presentation_soa d;
-    d.challenge = rowp(0);
-    d.responses = rowp(row_resp);
-    d.C_x_0 = rowp(row_cx); d.C_x_1 = rowp(row_cx + 1); d.C_V = rowp(row_cx + 2);
-    d.C_y = rowp(row_cy);
-    d.attr_values = rowp(row_av);
+    view_rows(d, dm, rowp, 0);
     std::vector<afx_encproof_soa> encs(sh.n_enc_proofs);
-    for (uint32_t e = 0; e < sh.n_enc_proofs; e++) {
-      const uint32_t r = row_enc + 14 * e;
-      encs[e] = { rowp(r), rowp(r + 1), rowp(r + 7), rowp(r + 8), rowp(r + 9), rowp(r + 10), rowp(r + 11), rowp(r + 12), rowp(r + 13) };
-    }
+    for (uint32_t e = 0; e < sh.n_enc_proofs; e++) view_rows(encs[e], dm, rowp, row_enc + ENC_ROWS * e);
     d.enc = encs.data();
     if ((rc2 = afx_verify_presentations_dev(ctx, &sh, &d, dn, st.dev(o_st)))) return rc2;
     return st.fetch_all();

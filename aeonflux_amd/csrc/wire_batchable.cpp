@@ -8,13 +8,15 @@
 #include <map>
 #include "records.hpp"
 #include "wire_formats.hpp"
+#include "batch_arrays.hpp"
 
 namespace {
 // Rows of the struct-of-arrays scratch both doors use, in record order but for the revealed values:
-//   R[n_main] | responses[nr] | C_x_0 C_x_1 C_V | C_y[na] | per proof of encryption: R[5] responses[6] pk E1 E2 C_y_1 C_y_2 C_y_3 C_y_2p
+//   R[n_main] | responses[nr] | C_x_0 C_x_1 C_V | C_y[na] | per proof of encryption: R[5] and the proof's rows but its challenge
+constexpr uint32_t PER_PROOF_ROWS = CM_ENC_ROWS + ENC_ROWS - 1;   // 18
 struct Rows {
-  uint32_t resp, cx, cy, enc, end;
-  Rows(const afx_shape& sh, uint32_t n_main) : resp(n_main), cx(resp + sh.n_responses), cy(cx + 3), enc(cy + sh.n_attributes), end(enc + 18 * sh.n_enc_proofs) {}
+  uint32_t resp, enc, end;
+  Rows(const afx_shape& sh, uint32_t n_main) : resp(n_main), enc(resp + sh.n_responses + 3 + sh.n_attributes), end(enc + PER_PROOF_ROWS * sh.n_enc_proofs) {}
 };
 }  // namespace
 
@@ -50,23 +52,17 @@ extern "C" int afx_batchable_wire_pack(const afx_shape* shape, const afx_present
   if (blob_cap < len) { set_error("blob buffer too small"); return AFX_E_BAD_ARGS; }
   const afx_shape& sh = *shape;
   const afx_presentation_soa& b = *batch;
-  bool missing = count && (!cm->main || !b.C_x_0 || !b.C_x_1 || !b.C_V || (sh.n_attributes && !b.C_y) || (sh.n_responses && !b.responses) || (sh.n_enc_proofs && (!b.enc || !cm->enc)));
-  for (uint32_t i = 0; i < sh.n_attributes; i++)
-    if (revealed(sh.kinds[i]) && count && !b.attr_values) missing = true;
-  for (uint32_t e = 0; e < sh.n_enc_proofs && !missing && count; e++) {
-    const afx_encproof_soa& q = b.enc[e];
-    missing |= !cm->enc[e] || !q.responses || !q.pk || !q.E1 || !q.E2 || !q.C_y_1 || !q.C_y_2 || !q.C_y_3 || !q.C_y_2p;
-  }
-  if (missing) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
+  const Dims dm = dims_of(sh);
+  if (count && batchable_any_null(b, *cm, dm)) { set_error("null batch array"); return AFX_E_BAD_ARGS; }
   write_header(FORMATS[AFXB], blob, sh, count, cells, n_main);
+  if (!count) return AFX_OK;   // (no record: no array is looked at)
   std::vector<const uint8_t*> col;
-  auto rows = [&](const uint8_t* base, uint32_t k) { for (uint32_t r = 0; r < k; r++) col.push_back(base + (size_t)r * count * 32); };
-  rows(cm->main, n_main); rows(b.responses, sh.n_responses); rows(b.C_x_0, 1); rows(b.C_x_1, 1); rows(b.C_V, 1); rows(b.C_y, sh.n_attributes);
-  for (uint32_t i = 0; i < sh.n_attributes; i++)
-    if (revealed(sh.kinds[i])) col.push_back(b.attr_values + (size_t)i * count * 32);
+  auto cell = [&](const uint8_t* base, uint32_t r) { col.push_back(base + (size_t)r * count * 32); };
+  for (uint32_t r = 0; r < n_main; r++) cell(cm->main, r);
+  each_cell(b, dm, cell, NO_CHALLENGE);
   for (uint32_t e = 0; e < sh.n_enc_proofs; e++) {
-    const afx_encproof_soa& q = b.enc[e];
-    rows(cm->enc[e], 5); rows(q.responses, 6); rows(q.pk, 1); rows(q.E1, 1); rows(q.E2, 1); rows(q.C_y_1, 1); rows(q.C_y_2, 1); rows(q.C_y_3, 1); rows(q.C_y_2p, 1);
+    for (uint32_t r = 0; r < CM_ENC_ROWS; r++) cell(cm->enc[e], r);
+    each_cell(b.enc[e], dm, cell, NO_CHALLENGE);
   }
   if (col.size() != cells) { set_error("internal: wire cell list"); return AFX_E_BAD_ARGS; }
   uint8_t* rec = blob + hdr;
@@ -93,7 +89,7 @@ int verify_group(afx_ctx* ctx, const VGroup& G, const afx_device_rng& rng, uint8
   const afx_shape& sh = G.sh;
   const Rows R(sh, G.n_main);
   const uint32_t values_row = R.end, rows = values_row + sh.n_attributes;
-  const std::vector<uint32_t> map = presentation_map(sh, R.resp, 18, values_row, R.enc);
+  const std::vector<uint32_t> map = presentation_map(sh, R.resp, PER_PROOF_ROWS, values_row, R.enc);
   if (map.size() != G.cells) { set_error("internal: AFXB cell map"); return AFX_E_BAD_ARGS; }
   const size_t n = G.total;
   std::vector<Stager::Piece> pieces;
@@ -106,14 +102,17 @@ int verify_group(afx_ctx* ctx, const VGroup& G, const afx_device_rng& rng, uint8
   if (rc) return rc;
   if ((rc = transpose_in(st, o_rec, o_soa, o_map, G.cells, n))) return rc;   // (a Stager of the call's own: at once)
   auto rowp = [&](uint32_t r) { return st.dev(o_soa) + (size_t)r * n * 32; };
+  const Dims dm = dims_of(sh);
   std::vector<afx_encproof_soa> encs(sh.n_enc_proofs);
   std::vector<uint8_t*> cenc(sh.n_enc_proofs);
   for (uint32_t e = 0; e < sh.n_enc_proofs; e++) {
-    const uint32_t r = R.enc + 18 * e;
+    const uint32_t r = R.enc + PER_PROOF_ROWS * e;
     cenc[e] = rowp(r);
-    encs[e] = { nullptr, rowp(r + 5), rowp(r + 11), rowp(r + 12), rowp(r + 13), rowp(r + 14), rowp(r + 15), rowp(r + 16), rowp(r + 17) };
+    encs[e].challenge = nullptr;
+    view_rows(encs[e], dm, rowp, r + CM_ENC_ROWS, NO_CHALLENGE);
   }
-  const afx_presentation_soa d = { nullptr, rowp(R.resp), rowp(R.cx), rowp(R.cx + 1), rowp(R.cx + 2), rowp(R.cy), rowp(values_row), encs.data() };
+  afx_presentation_soa d = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rowp(values_row), encs.data() };
+  view_rows(d, dm, rowp, R.resp, NO_CHALLENGE, NO_VALUES);
   const afx_commitments_soa dcm = { rowp(0), cenc.data() };
   if ((rc = afx_verify_presentations_batchable_dev(ctx, &sh, &d, &dcm, &rng, n, st.dev(o_st)))) return rc;
   std::vector<uint8_t> got(n);
@@ -212,38 +211,42 @@ int show_group(afx_ctx* ctx, const afx_show_group& G, const BJob& J, uint8_t* re
   const afx_credentials_soa& cr = G.creds;
   const afx_shape& sh = J.sh;
   const size_t n = G.count;
-  const uint32_t na = sh.n_attributes, nsp = sh.n_enc_proofs;
+  const uint32_t nsp = sh.n_enc_proofs;
   const bool kp = G.keypairs && nsp;
   const Rows R(sh, J.n_main);
   const uint32_t chal = R.end, values_row = (chal + 1 + nsp + 7) & ~7u;   // the compact challenges (written, not sent), then pad: values_row * n * 32 is a multiple of 256
-  const std::vector<uint32_t> map = presentation_map(sh, R.resp, 18, values_row, R.enc);
+  const std::vector<uint32_t> map = presentation_map(sh, R.resp, PER_PROOF_ROWS, values_row, R.enc);
   if (map.size() != J.cells) { set_error("internal: AFXB show cell map"); return AFX_E_BAD_ARGS; }
   Stager st(ctx);
-  auto in = [&](const uint8_t* p, size_t k, size_t elem) { return st.add(p, k * n * elem); };
-  const size_t o_soa = st.reserve(n * values_row * 32), o_val = in(cr.values, na, 32), o_map = st.add((const uint8_t*)map.data(), 4 * map.size());
-  const size_t o_M2 = nsp ? in(cr.M2, na, 32) : 0, o_m3 = nsp ? in(cr.m3, na, 32) : 0, o_t = in(cr.t, 1, 32), o_U = in(cr.U, 1, 32), o_V = in(cr.V, 1, 32);
-  const size_t o_zw = in(G.rnd.z_wide, 1, 64), o_seed = in(G.rnd.rng_seed, 1, 32), o_es = nsp ? in(G.rnd.enc_seeds, nsp, 32) : 0;
-  size_t o_kp[4] = { 0, 0, 0, 0 };
-  if (kp) { o_kp[0] = in(G.keypairs->a, 1, 32); o_kp[1] = in(G.keypairs->a0, 1, 32); o_kp[2] = in(G.keypairs->a1, 1, 32); o_kp[3] = in(G.keypairs->pk, 1, 32); }
+  const Dims dm = dims_of(cr);
+  auto in = [&](const uint8_t* p, size_t k, size_t elem) { return p ? st.add(p, k * n * elem) : NO_ARRAY; };   // (an array the layout does not read: nothing staged)
+  const size_t o_soa = st.reserve(n * values_row * 32);
+  Offsets<afx_credentials_soa> oc;
+  stage(oc, cr, dm, in, 0, 1);   // the value rows, right behind the scratch
+  const size_t o_map = st.add((const uint8_t*)map.data(), 4 * map.size());
+  stage(oc, cr, dm, in, 1);
+  const Offsets<afx_show_randomness> orn = stage(G.rnd, dm, in);
+  Offsets<afx_keypairs_soa> ok;
+  if (kp) stage(ok, *G.keypairs, dm, in);
   const size_t o_out = st.add(nullptr, n * J.cells * 32), o_st = st.add(nullptr, n);
   int rc = st.upload();
   if (rc) return rc;
   uint8_t* soa_d = st.dev(o_soa);
-  if (st.dev(o_val) != soa_d + (size_t)values_row * n * 32) { set_error("internal: value rows are not behind the show scratch"); return AFX_E_BAD_ARGS; }
+  if (st.dev(oc.at[0]) != soa_d + (size_t)values_row * n * 32) { set_error("internal: value rows are not behind the show scratch"); return AFX_E_BAD_ARGS; }
   auto rowp = [&](uint32_t r) { return soa_d + (size_t)r * n * 32; };
-  afx_credentials_soa dc = cr;
-  dc.values = st.dev(o_val); dc.M2 = nsp ? st.dev(o_M2) : nullptr; dc.m3 = nsp ? st.dev(o_m3) : nullptr;
-  dc.t = st.dev(o_t); dc.U = st.dev(o_U); dc.V = st.dev(o_V);
-  const afx_keypairs_soa dk = { st.dev(o_kp[0]), st.dev(o_kp[1]), st.dev(o_kp[2]), st.dev(o_kp[3]) };
-  const afx_show_randomness dr = { st.dev(o_zw), st.dev(o_seed), nsp ? st.dev(o_es) : nullptr };
+  const afx_credentials_soa dc = on_device(st, oc, cr);
+  const afx_keypairs_soa dk = on_device(st, ok);
+  const afx_show_randomness dr = on_device(st, orn);
   std::vector<afx_encproof_out> de(nsp);
   std::vector<uint8_t*> ce(nsp);
   for (uint32_t e = 0; e < nsp; e++) {
-    const uint32_t r = R.enc + 18 * e;
+    const uint32_t r = R.enc + PER_PROOF_ROWS * e;
     ce[e] = rowp(r);
-    de[e] = { rowp(chal + 1 + e), rowp(r + 5), rowp(r + 11), rowp(r + 12), rowp(r + 13), rowp(r + 14), rowp(r + 15), rowp(r + 16), rowp(r + 17) };
+    de[e].challenge = rowp(chal + 1 + e);
+    view_rows(de[e], dm, rowp, r + CM_ENC_ROWS, NO_CHALLENGE);
   }
-  const afx_presentation_out dout = { rowp(chal), rowp(R.resp), rowp(R.cx), rowp(R.cx + 1), rowp(R.cx + 2), rowp(R.cy), nullptr, nsp ? de.data() : nullptr };
+  afx_presentation_out dout = { rowp(chal), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nsp ? de.data() : nullptr };
+  view_rows(dout, dm, rowp, R.resp, NO_CHALLENGE, NO_VALUES);
   const afx_commitments_soa dcm = { rowp(0), ce.data() };
   afx_shape shape_dev;
   if ((rc = afx_show_batchable_dev(ctx, &dc, kp ? &dk : nullptr, &dr, n, &dout, &dcm, &shape_dev, st.dev(o_st)))) return rc;

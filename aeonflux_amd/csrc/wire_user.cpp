@@ -13,6 +13,7 @@
 #include <vector>
 #include "records.hpp"
 #include "wire_formats.hpp"
+#include "batch_arrays.hpp"
 
 namespace {
 
@@ -258,7 +259,8 @@ int show_records(afx_ctx* ctx, const SJob& J, size_t first, size_t n, const uint
   const afx_shape& sh = J.sh;
   const uint32_t na = sh.n_attributes, nr = sh.n_responses, nsp = sh.n_enc_proofs, cells = J.cells;
   const bool kp = G.keypairs && nsp;
-  const uint32_t r_x = 1 + nr, r_cy = r_x + 3, r_enc = r_cy + na, rows = r_enc + 14 * nsp, r_val = (rows + 7) & ~7u;   // (r_val * dn * 32: a multiple of 256)
+  const Dims dm = dims_of(cr);
+  const uint32_t r_enc = 1 + nr + 3 + na, rows = r_enc + ENC_ROWS * nsp, r_val = (rows + 7) & ~7u;   // (r_val * dn * 32: a multiple of 256)
   const std::vector<uint32_t> map = presentation_map(sh, 1, 14, r_val, r_enc);
   if (map.size() != cells) { set_error("internal: show wire cell map"); return AFX_E_BAD_ARGS; }
   struct { uint32_t n; uint8_t kinds[AFX_MAX_ATTRIBUTES]; } jd;   // what makes two calls one pass (statements.hpp host_pipe)
@@ -271,40 +273,39 @@ int show_records(afx_ctx* ctx, const SJob& J, size_t first, size_t n, const uint
     const size_t f0 = first + off;
     st.layout_tag = seed40 ? 5 : 3;
     const size_t dn = st.dev_items(sn);
-    auto in = [&](const uint8_t* p, size_t k, size_t elem) { return st.add_rows(p, k, elem, total, f0, sn, dn); };
-    const size_t o_soa = st.reserve(dn * r_val * 32), o_val = in(cr.values, na, 32), o_map = st.add((const uint8_t*)map.data(), 4 * (size_t)cells);
-    const size_t o_M2 = nsp ? in(cr.M2, na, 32) : 0, o_m3 = nsp ? in(cr.m3, na, 32) : 0, o_t = in(cr.t, 1, 32), o_U = in(cr.U, 1, 32), o_V = in(cr.V, 1, 32);
-    size_t o_zw, o_seed, o_es = 0;
+    auto in = [&](const uint8_t* p, size_t k, size_t elem) { return p ? st.add_rows(p, k, elem, total, f0, sn, dn) : NO_ARRAY; };   // (an array the layout does not read: nothing staged)
+    const size_t o_soa = st.reserve(dn * r_val * 32);
+    Offsets<afx_credentials_soa> oc;
+    stage(oc, cr, dm, in, 0, 1);   // the value rows, right behind the scratch
+    const size_t o_map = st.add((const uint8_t*)map.data(), 4 * (size_t)cells);
+    stage(oc, cr, dm, in, 1);
+    Offsets<afx_show_randomness> orn;
     if (seed40) {
       const size_t s_at = st.add_seed(seed40, dn);
-      o_zw = st.add_drawn(s_at, AFX_DRAW_Z_WIDE, 1, draws, f0, sn, dn);
-      o_seed = st.add_drawn(s_at, AFX_DRAW_SHOW_SEED, 1, draws, f0, sn, dn);
-      if (nsp) o_es = st.add_drawn(s_at, AFX_DRAW_ENC_SEED(0), nsp, draws, f0, sn, dn);
+      orn.at[0] = st.add_drawn(s_at, AFX_DRAW_Z_WIDE, 1, draws, f0, sn, dn);
+      orn.at[1] = st.add_drawn(s_at, AFX_DRAW_SHOW_SEED, 1, draws, f0, sn, dn);
+      if (nsp) orn.at[2] = st.add_drawn(s_at, AFX_DRAW_ENC_SEED(0), nsp, draws, f0, sn, dn);
     } else {
-      o_zw = in(G.rnd.z_wide, 1, 64); o_seed = in(G.rnd.rng_seed, 1, 32); o_es = nsp ? in(G.rnd.enc_seeds, nsp, 32) : 0;
+      stage(orn, G.rnd, dm, in);
     }
-    size_t o_kp[4] = { 0, 0, 0, 0 };
-    if (kp) { o_kp[0] = in(G.keypairs->a, 1, 32); o_kp[1] = in(G.keypairs->a0, 1, 32); o_kp[2] = in(G.keypairs->a1, 1, 32); o_kp[3] = in(G.keypairs->pk, 1, 32); }
+    Offsets<afx_keypairs_soa> ok;
+    if (kp) stage(ok, *G.keypairs, dm, in);
     const size_t o_out = st.add_rows(nullptr, 1, (size_t)cells * 32, total, f0, sn, dn), o_st = st.add(nullptr, dn);
     st.plan_fetch(J.rec, o_out, 1, (size_t)cells * 32, total, f0, sn, dn);
     st.plan_fetch(J.status, o_st, 1, 1, total, f0, sn, dn);
     int rc = st.upload();
     if (rc) return rc;
     uint8_t* soa_d = st.dev(o_soa);
-    if (st.dev(o_val) != soa_d + (size_t)r_val * dn * 32) { set_error("internal: value rows are not behind the show scratch"); return AFX_E_BAD_ARGS; }
+    if (st.dev(oc.at[0]) != soa_d + (size_t)r_val * dn * 32) { set_error("internal: value rows are not behind the show scratch"); return AFX_E_BAD_ARGS; }
     auto rowp = [&](uint32_t r) { return soa_d + (size_t)r * dn * 32; };
-    afx_credentials_soa dc = cr;
-    dc.values = st.dev(o_val); dc.M2 = nsp ? st.dev(o_M2) : nullptr; dc.m3 = nsp ? st.dev(o_m3) : nullptr;
-    dc.t = st.dev(o_t); dc.U = st.dev(o_U); dc.V = st.dev(o_V);
-    const afx_keypairs_soa dk = { st.dev(o_kp[0]), st.dev(o_kp[1]), st.dev(o_kp[2]), st.dev(o_kp[3]) };
-    const afx_show_randomness dr = { st.dev(o_zw), st.dev(o_seed), nsp ? st.dev(o_es) : nullptr };
+    const afx_credentials_soa dc = on_device(st, oc, cr);
+    const afx_keypairs_soa dk = on_device(st, ok);
+    const afx_show_randomness dr = on_device(st, orn);
     std::vector<afx_encproof_out> de(nsp);
-    for (uint32_t e = 0; e < nsp; e++) {
-      const uint32_t r = r_enc + 14 * e;
-      de[e] = { rowp(r), rowp(r + 1), rowp(r + 7), rowp(r + 8), rowp(r + 9), rowp(r + 10), rowp(r + 11), rowp(r + 12), rowp(r + 13) };
-    }
+    for (uint32_t e = 0; e < nsp; e++) view_rows(de[e], dm, rowp, r_enc + ENC_ROWS * e);
     // (attr_values == null: the revealed values are not copied - their cells read the value rows)
-    const afx_presentation_out dout = { rowp(0), rowp(1), rowp(r_x), rowp(r_x + 1), rowp(r_x + 2), rowp(r_cy), nullptr, nsp ? de.data() : nullptr };
+    afx_presentation_out dout = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nsp ? de.data() : nullptr };
+    view_rows(dout, dm, rowp, 0, 0, NO_VALUES);
     afx_shape shape_dev;
     if ((rc = afx_show_dev(ctx, &dc, kp ? &dk : nullptr, &dr, dn, &dout, &shape_dev, st.dev(o_st)))) return rc;
     if ((rc = transpose_out(st, o_soa, o_out, o_map, o_st, cells, dn))) return rc;
